@@ -5,13 +5,16 @@ One step = the reference's training micro-step (scripts/train.py:127-143) on one
 GPU: forward -> DiceBCELoss -> backward -> (DDP all-reduce) -> clip_grad_norm_(1.0) -> AdamW.step
 -> zero_grad.  Inputs are generated once and stay resident in HBM.
 
-  python bench.py [--gpus N --steps K --warmup W]
+  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
       --master-port P bench.py --gpus N --steps K --warmup W
 
-Rank 0 prints one JSON line (value = whole-job images/s, max-over-ranks time).  The line carries
-`roofline` (the dominant kernel, timed live with HIP events on its launch stream) and
-`cpu_baseline` (the CPU oracle timed on a bounded sample on this host, rank 0 at N=1 only).
+Rank 0 prints one JSON line (value = whole-job images/s, max-over-ranks time).  A plain run sets up,
+warms up, times the K steps, writes the last step's outputs if --dump-outputs is given, and prints
+the line.  With --full the line also carries `roofline` (the dominant kernel, timed live with HIP
+events on its launch stream), `hbm`, `without_optimizer`, `graphed_step`, `fp32_operands` and
+`cpu_baseline` (the CPU oracle timed on a bounded sample on this host, rank 0 at N=1 only), each
+measured in passes of its own after the headline loop.
 """
 
 from __future__ import annotations
@@ -205,6 +208,35 @@ def max_over_ranks(elapsed: float, device: torch.device) -> float:
     return float(te)
 
 
+DUMP_MAX_ELEMS = 4 << 20   # per array (16 MiB as float32): loss + logits + params + buffers stay under 64 MB
+
+
+def dump_outputs(out_dir: str, loss: torch.Tensor, logits: torch.Tensor, model: torch.nn.Module) -> dict:
+    """What a caller of the timed step holds after its last call, as <out_dir>/<name>.npy in float32: the loss
+    it returned, the logits of its forward, and the state it updated in place (the parameters after AdamW and
+    the BatchNorm running statistics, each flattened in module order).  An array of more than DUMP_MAX_ELEMS
+    elements is written as a fixed sample of that many (sorted indices from a seeded generator, the same in
+    every run)."""
+    import numpy as np
+
+    def flat(ts):
+        return torch.cat([v.detach().reshape(-1).float() for v in ts])
+
+    arrays = {"loss": loss.detach().reshape(1).float(), "logits": logits.detach().float(),
+              "params": flat(model.parameters()), "buffers": flat(model.buffers())}
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    shapes = {}
+    for k, (name, a) in enumerate(arrays.items()):
+        if a.numel() > DUMP_MAX_ELEMS:
+            g = torch.Generator().manual_seed(4321 + k)
+            idx = torch.randint(0, a.numel(), (DUMP_MAX_ELEMS,), generator=g).sort().values
+            a = a.reshape(-1)[idx.to(a.device)]
+        np.save(d / f"{name}.npy", a.cpu().numpy())
+        shapes[name] = list(a.shape)
+    return shapes
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -219,6 +251,12 @@ def main():
                     help="operand type; fp16 adds dynamic loss scaling (torch.amp.GradScaler), as C5 asks")
     ap.add_argument("--probe", default=None, help="kernel family to time live (default: conv_kernel<prec,3,64>)")
     ap.add_argument("--bucket-mb", type=float, default=25.0, help="DDP bucket_cap_mb (N>1)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the last step's outputs as DIR/<name>.npy (rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline loop also measure, in passes of their own: the conv family's roofline, "
+                         "the HBM-bound kernels, the rate without the optimizer, the HIP-graph replay, the fp32-operand "
+                         "rate and the CPU baseline (--probe, --no-* and --cpu-* select among them)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-iters", type=int, default=3)
     ap.add_argument("--cpu-batch", type=int, default=4)
@@ -276,13 +314,15 @@ def main():
             last = k == args.accum - 1
             ctx = net.no_sync() if (world > 1 and not last) else contextlib.nullcontext()
             with ctx:
-                loss = crit(net(x), t)
+                logits = net(x)
+                loss = crit(logits, t)
                 scaler.scale(loss / args.accum if args.accum > 1 else loss).backward()
         scaler.unscale_(opt)
         torch.nn.utils.clip_grad_norm_(params, 1.0)
         scaler.step(opt)
         scaler.update()
         opt.zero_grad(set_to_none=True)
+        step.logits = logits.detach()     # for --dump-outputs (a view without the autograd graph)
         return loss
 
     def timed(fn, steps):
@@ -302,7 +342,42 @@ def main():
         step()
     elapsed, loss = timed(step, args.steps)          # the headline: no probe events inside
     final_loss = round(float(loss.detach()), 5)
+    dumped = dump_outputs(args.dump_outputs, loss, step.logits, model) if (args.dump_outputs and rank == 0) else None
     del loss     # the last step's autograd graph (its AccumulateGrad nodes) must not outlive the step
+
+    images = world * args.batch * args.accum * args.steps
+    value = images / elapsed
+    headline = (args.size, args.in_ch, args.accum, args.model) == (512, 1, 1, "attention_unet")
+    metric = METRIC if headline else (
+        f"{args.size}x{args.size} {args.in_ch}-ch slices/sec fwd+bwd, {'AttentionUNet' if args.model == 'attention_unet' else 'UNet'} "
+        f"bs={args.batch}/GPU x grad-accum {args.accum}, {args.precision}, 1/2/4/8 MI355X")
+    fpi = FLOPS_PER_IMAGE[args.model] if (args.size, args.in_ch) == (512, 1) else (
+        FLOPS_PER_IMAGE_C5 if (args.size, args.in_ch, args.model) == (1024, 3, "attention_unet") else None)
+    line = {
+        "metric": metric,
+        "value": round(value, 3), "unit": "img/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(elapsed / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": args.precision, "data": "synthetic (x~U(-1,1), 1-3 disc masks/img; seeded)",
+        "config": {"workload": f"{args.model} {args.in_ch}x{args.size}x{args.size} train step "
+                               f"(fwd+DiceBCE+bwd{' x%d accum' % args.accum if args.accum > 1 else ''}+clip+AdamW"
+                               f"{'; GradScaler' if scaler.is_enabled() else ''})",
+                   "model": args.model, "global_batch": world * args.batch * args.accum, "per_gpu_batch": args.batch,
+                   "grad_accum": args.accum, "image": [args.in_ch, args.size, args.size],
+                   "parallelism": f"dp{world}" if world > 1 else "single",
+                   "grad_sync": f"torch DDP ({backend}, bucket {args.bucket_mb:g} MB)" if world > 1 else None},
+        "whole_step_tflops": round(value * fpi / 1e12, 2) if fpi else None,
+        "final_loss": final_loss,
+    }
+    if dumped is not None:
+        line["dumped_outputs"] = {"dir": args.dump_outputs, "shapes": dumped}
+    if scaler.is_enabled():
+        line["loss_scale"] = float(scaler.get_scale())
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
 
     # the dominant kernel family, timed live in a separate pass of the same steps: every 16-bit 3x3 conv
     # launch (fwd + dgrad; the 32x32x16-MFMA conv5_kernel tiles on the large maps, their 128-output-channel
@@ -335,8 +410,6 @@ def main():
     fwd_bwd()
     el_nb, _ = timed(fwd_bwd, args.steps)
 
-    images = world * args.batch * args.accum * args.steps
-    value = images / elapsed
     peak = MFMA_PEAK_TFLOPS[args.precision]
     achieved = ps["tflops"] or 0.0
     traffic = None
@@ -348,25 +421,7 @@ def main():
         ent = tr.get(f"{target}@{args.size}x{args.in_ch}") or (
             tr.get(target) if args.model == "attention_unet" else tr.get(f"{target}@unet"))
         traffic = ent.get("bytes_per_launch") if isinstance(ent, dict) else ent
-    headline = (args.size, args.in_ch, args.accum, args.model) == (512, 1, 1, "attention_unet")
-    metric = METRIC if headline else (
-        f"{args.size}x{args.size} {args.in_ch}-ch slices/sec fwd+bwd, {'AttentionUNet' if args.model == 'attention_unet' else 'UNet'} "
-        f"bs={args.batch}/GPU x grad-accum {args.accum}, {args.precision}, 1/2/4/8 MI355X")
-    fpi = FLOPS_PER_IMAGE[args.model] if (args.size, args.in_ch) == (512, 1) else (
-        FLOPS_PER_IMAGE_C5 if (args.size, args.in_ch, args.model) == (1024, 3, "attention_unet") else None)
-    line = {
-        "metric": metric,
-        "value": round(value, 3), "unit": "img/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(elapsed / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": args.precision, "data": "synthetic (x~U(-1,1), 1-3 disc masks/img; seeded)",
-        "config": {"workload": f"{args.model} {args.in_ch}x{args.size}x{args.size} train step "
-                               f"(fwd+DiceBCE+bwd{' x%d accum' % args.accum if args.accum > 1 else ''}+clip+AdamW"
-                               f"{'; GradScaler' if scaler.is_enabled() else ''})",
-                   "model": args.model, "global_batch": world * args.batch * args.accum, "per_gpu_batch": args.batch,
-                   "grad_accum": args.accum, "image": [args.in_ch, args.size, args.size],
-                   "parallelism": f"dp{world}" if world > 1 else "single",
-                   "grad_sync": f"torch DDP ({backend}, bucket {args.bucket_mb:g} MB)" if world > 1 else None},
-        "whole_step_tflops": round(value * fpi / 1e12, 2) if fpi else None,
+    line.update({
         "roofline": {"kernel": target, "bound": "mfma", "achieved": round(achieved, 2), "peak": peak,
                      "unit": "TFLOP/s", "frac": round(achieved / peak, 4), "traffic": traffic,
                      "traffic_unit": "HBM bytes/launch (rocprofv3 PMC, profiles/traffic.json)",
@@ -377,11 +432,10 @@ def main():
                 "note": "algorithmic bytes (each operand read once, each output written once) / HIP-event time "
                         "per launch, separate pass; measured_bytes_per_launch: rocprofv3 FETCH_SIZE x2 + "
                         "WRITE_SIZE (profiles/traffic.json)"},
-        "final_loss": final_loss,
         "without_optimizer": {"value": round(world * args.batch * args.accum * args.steps / el_nb, 3),
                               "ms_per_step": round(el_nb / args.steps * 1e3, 3),
                               "note": "fwd+DiceBCE+bwd (+grad averaging), no clip/AdamW"},
-    }
+    })
     if scaler.is_enabled():
         line["loss_scale"] = float(scaler.get_scale())
     if world == 1 and args.accum == 1 and not scaler.is_enabled() and not args.no_graph_line:

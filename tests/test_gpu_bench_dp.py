@@ -28,7 +28,7 @@ def test_bench_two_ranks_gloo():
     env = dict(os.environ, UNET_DIST_BACKEND="gloo", OMP_NUM_THREADS="4")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), str(ROOT / "bench.py"),
-           "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "1", "--size", "128"]
+           "--full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "1", "--size", "128"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

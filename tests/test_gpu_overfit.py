@@ -21,7 +21,8 @@ reference's own measured spread:
     model — the eval forward gives the same labels (any difference only at near ties |z1 - z0| < 1e-4, counted)
     hence the same Tumor-Dice, and one training step from each state has the reference's loss and gradients no
     further from fp64 than the reference's own fp32 step (3x + 1e-5);
-  * test_overfit_c1_tumor_dice_vs_reference_spread: the first 16 epochs step for step;
+  * test_overfit_c1_tumor_dice_vs_reference_spread: the first 16 epochs step for step, against the reference's
+    recorded fp32 and fp64 executions (tests/golden/overfit_c1_16ep.json);
   * test_overfit_c1_full_protocol_final_dice: 200 epochs from the seeded weights; the last-epoch Tumor-Dice
     within 5e-3 of the fp64 oracle started from the same weights (|diff| printed against the north_star's 1e-3)
     and no lower than the reference fp32 ensemble's lowest member - 1e-3;
@@ -31,6 +32,7 @@ reference's own measured spread:
 
 import contextlib
 import itertools
+import json
 import sys
 from pathlib import Path
 
@@ -62,11 +64,18 @@ def c1():
 
 def test_overfit_c1_tumor_dice_vs_reference_spread(c1):
     """The first 16 epochs (Dice rises from 0.01 to ~0.97): at every epoch our Tumor-Dice and loss are within
-    max(1e-3, 1.5 S) of the fp32 reference, S the reference's own largest fp32-vs-fp64 spread in that window."""
+    max(1e-3, 1.5 S) of the fp32 reference, S the reference's own largest fp32-vs-fp64 spread in that window.
+
+    The reference's two executions are recorded ones (tests/golden/overfit_c1_16ep.json, written by
+    `tools/overfit_diag.py record`): its fp32 ATen / MIOpen execution is not reproducible from run to run (MIOpen
+    picks its convolution algorithms at run time), and around epoch 5, where the Dice jumps from 0.08
+    to 0.96, another draw of it moved its Dice by 1.6e-2 (0.0777 -> 0.0942), more than this bound, whatever the HIP path does.  The HIP
+    path gives the same bits on every box, so against the recorded reference the test is deterministic."""
     D, init, names, x, t = c1
+    rec = json.loads((Path(__file__).resolve().parent / "golden" / "overfit_c1_16ep.json").read_text())
+    assert rec["epochs"] == EPOCHS
     hip = D.run_hip(init, x, t, EPOCHS, 64)
-    r32 = D.run_oracle(init, names, x, t, EPOCHS, torch.float32)
-    r64 = D.run_oracle(init, names, x, t, EPOCHS, torch.float64)
+    r32, r64 = rec["ref32"], rec["ref64"]
     print("\nepoch loss_hip loss_ref32 loss_ref64 | dice_hip dice_ref32 dice_ref64")
     for i in range(EPOCHS):
         print(i, *("%.6f" % v for v in (hip[i][0], r32[i][0], r64[i][0], hip[i][1], r32[i][1], r64[i][1])))

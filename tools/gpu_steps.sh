@@ -21,19 +21,19 @@ for step in ${STEPS:-tests smoke bench}; do
     timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || fail smoke $O/smoke.log
     tail -1 $O/smoke.log ;;
   bench)   # the driver's default bench line
-    timeout -k 10 400 python -u bench.py > $O/bench.json 2> $O/bench.err || fail bench $O/bench.err
+    timeout -k 10 400 python -u bench.py --full > $O/bench.json 2> $O/bench.err || fail bench $O/bench.err
     cat $O/bench.json ;;
   benchq)  # a quick headline-only line
-    timeout -k 10 300 python -u bench.py --no-cpu-baseline --no-fp32-line --no-graph-line ${BARGS} > $O/benchq.json 2> $O/benchq.err || fail benchq $O/benchq.err
+    timeout -k 10 300 python -u bench.py --full --no-cpu-baseline --no-fp32-line --no-graph-line ${BARGS} > $O/benchq.json 2> $O/benchq.err || fail benchq $O/benchq.err
     cat $O/benchq.json ;;
   c5)
-    timeout -k 10 300 python -u bench.py --precision fp16 --in-ch 3 --size 1024 --accum 8 --steps 5 --warmup 2 --no-cpu-baseline --no-fp32-line > $O/bench_c5.json 2> $O/bench_c5.err || fail c5 $O/bench_c5.err
+    timeout -k 10 300 python -u bench.py --full --precision fp16 --in-ch 3 --size 1024 --accum 8 --steps 5 --warmup 2 --no-cpu-baseline --no-fp32-line > $O/bench_c5.json 2> $O/bench_c5.err || fail c5 $O/bench_c5.err
     cat $O/bench_c5.json ;;
   c2)
-    timeout -k 10 300 python -u bench.py --model unet --no-cpu-baseline --no-fp32-line --no-graph-line > $O/bench_c2.json 2> $O/bench_c2.err || fail c2 $O/bench_c2.err
+    timeout -k 10 300 python -u bench.py --full --model unet --no-cpu-baseline --no-fp32-line --no-graph-line > $O/bench_c2.json 2> $O/bench_c2.err || fail c2 $O/bench_c2.err
     cat $O/bench_c2.json ;;
   trace)   # kernel-trace stats of the bench command
-    timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o run -- python bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-fp32-line --no-graph-line > $O/trace.log 2>&1 || fail trace $O/trace.log
+    timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o run -- python bench.py --full --steps 30 --warmup 5 --no-cpu-baseline --no-fp32-line --no-graph-line > $O/trace.log 2>&1 || fail trace $O/trace.log
     # 78 traced steps: 5 warm-up + 30 timed + 10 probe + 2 hbm-probe + 31 fwd+bwd-only (without_optimizer)
     python tools/profsum.py $O/trace 78 45 "conv5_kernelIDF16b|conv5w_kernelIDF16b|conv3_kernelIDF16bLi3E|unet::conv5_kernel<" "conv5_splitk_finish_kernel" > $O/trace_summary.txt 2>&1; tail -3 $O/trace_summary.txt ;;
   layerprof)
@@ -43,7 +43,7 @@ for step in ${STEPS:-tests smoke bench}; do
     i=0
     for set in FETCH_SIZE WRITE_SIZE; do
       i=$((i+1))
-      timeout -s KILL 120 rocprofv3 --pmc $set --output-format csv -d $O/pmc$i -o pmc -- python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-fp32-line --no-graph-line > $O/pmc$i.log 2>&1 || fail "pmc pass $i" $O/pmc$i.log 5
+      timeout -s KILL 120 rocprofv3 --pmc $set --output-format csv -d $O/pmc$i -o pmc -- python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-fp32-line --no-graph-line > $O/pmc$i.log 2>&1 || fail "pmc pass $i" $O/pmc$i.log 5
     done
     python tools/traffic.py --all $O/pmc1 $O/pmc2 > $O/traffic.log 2>&1 || fail traffic $O/traffic.log
     cp profiles/traffic.json $O/traffic.json
@@ -52,7 +52,7 @@ for step in ${STEPS:-tests smoke bench}; do
     i=0
     for set in FETCH_SIZE WRITE_SIZE; do
       i=$((i+1))
-      timeout -s KILL 180 rocprofv3 --pmc $set --output-format csv -d $O/pmc5_$i -o pmc -- python bench.py --precision fp16 --in-ch 3 --size 1024 --steps 1 --warmup 1 --no-cpu-baseline --no-fp32-line --no-graph-line > $O/pmc5_$i.log 2>&1 || fail "pmc5 pass $i" $O/pmc5_$i.log 5
+      timeout -s KILL 180 rocprofv3 --pmc $set --output-format csv -d $O/pmc5_$i -o pmc -- python bench.py --full --precision fp16 --in-ch 3 --size 1024 --steps 1 --warmup 1 --no-cpu-baseline --no-fp32-line --no-graph-line > $O/pmc5_$i.log 2>&1 || fail "pmc5 pass $i" $O/pmc5_$i.log 5
     done
     python tools/traffic.py --all $O/pmc5_1 $O/pmc5_2 @1024x3 > $O/traffic5.log 2>&1 || fail traffic5 $O/traffic5.log
     cp profiles/traffic.json $O/traffic.json
@@ -68,7 +68,7 @@ for step in ${STEPS:-tests smoke bench}; do
       env $v timeout -k 10 300 python -u tools/layerprof.py > "$O/layerprof_${v//[^A-Za-z0-9]/_}.txt" 2>&1 || fail "ab layerprof $v" "$O/layerprof_${v//[^A-Za-z0-9]/_}.txt"
     done
     for v in "${ABA:-}" "${ABB:-}" ${ABC:+"$ABC"} "${ABA:-}"; do
-      env $v timeout -k 10 300 python -u bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-fp32-line --no-graph-line > $O/ab.json 2> $O/ab.err || fail "ab bench $v" $O/ab.err
+      env $v timeout -k 10 300 python -u bench.py --full --steps 30 --warmup 5 --no-cpu-baseline --no-fp32-line --no-graph-line > $O/ab.json 2> $O/ab.err || fail "ab bench $v" $O/ab.err
       echo "[$v] $(python -c "import json;d=json.load(open('$O/ab.json'));print(d['value'],d['ms_per_step'],d['roofline']['avg_us'])")"
     done ;;
   lp)      # layer timing under several environment settings (LPS: ';'-separated), summary lines matching LPGREP

@@ -14,7 +14,9 @@ Usage: python tools/overfit_diag.py MODE [args]
                                 weights perturbed by one ulp in a random half of their elements (the member-0 run
                                 unperturbed): the distribution of the last-epoch Tumor-Dice under rounding noise
   pin [epochs...]               the HIP eval forward / train step from the oracle's own states at those epochs:
-                                confusion counts vs the oracle's (near ties counted) and gradients vs fp64"""
+                                confusion counts vs the oracle's (near ties counted) and gradients vs fp64
+  record PATH [epochs]          the reference's fp32 and fp64 executions of the first epochs (default 16) from the
+                                seeded weights, as JSON: the fixture of tests/test_gpu_overfit.py's step-for-step test"""
 
 import sys
 import time
@@ -287,7 +289,7 @@ def ensemble(init, names, x, t, k, epochs, k64):
 
 def main():
     mode = sys.argv[1] if len(sys.argv) > 1 else "traj"
-    args = [int(a) for a in sys.argv[2:]]
+    args = [int(a) for a in sys.argv[(3 if mode == "record" else 2):]]
     if mode == "traj":
         epochs, base, size = (args + [40, 64, 512][len(args):])[:3]
         init, names, x, t = setup(base, size)
@@ -323,6 +325,17 @@ def main():
             print(f"  train step from it: loss HIP {r[0]:.7f} fp32 {r[1]:.7f} fp64 {r[2]:.7f}; grad rel-L2 vs fp64: "
                   f"HIP {r[3]:.3e}, oracle fp32 {r[4]:.3e}; running buffers vs fp64: HIP {r[5]:.3e}, fp32 {r[6]:.3e}",
                   flush=True)
+    elif mode == "record":
+        # tests/golden/overfit_c1_16ep.json: the reference's fp32 and fp64 executions of the first epochs, recorded
+        import json
+        path, epochs = sys.argv[2], args[0] if args else 16
+        init, names, x, t = setup()
+        rec = {"what": "tools/overfit_diag.py record: per-epoch [loss, Tumor-Dice] of the reference's network (the "
+                       "oracle's ATen ops on the GPU) from the seeded C1 weights and batch, in fp32 and in fp64",
+               "epochs": epochs, "torch": torch.__version__, "device": torch.cuda.get_device_name(0),
+               "ref32": [list(e) for e in run_oracle(init, names, x, t, epochs, torch.float32)],
+               "ref64": [list(e) for e in run_oracle(init, names, x, t, epochs, torch.float64)]}
+        Path(path).write_text(json.dumps(rec, indent=1) + "\n")
     else:
         raise SystemExit(__doc__)
 
