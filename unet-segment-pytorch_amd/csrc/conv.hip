@@ -16,6 +16,7 @@
 //    or routed through the 2x2 max-pool argmax).
 #include <stdio.h>
 #include "conv_src16.h"
+#include "paths.h"
 
 namespace unet {
 
@@ -414,7 +415,6 @@ __global__ __launch_bounds__(64 * WM * WN) void conv2_kernel(const unet_conv_des
 // ------------------------------------------------------------------------------------------------
 struct ConvCfg {
   int wm, wn, ntn, raw;
-  const char* name;
   int w4;  // bf16 3x3, plain/act sources: 4-wave 8-row conv3 tile with 8-row waves (two workgroups per CU)
 };
 
@@ -470,35 +470,33 @@ static int launch_conv2(const unet_conv_desc* d, hipStream_t st) {
   return check_launch("conv");
 }
 
+// the kernel's template tuple of a block tile: conv2 runs it as it is (4-row waves); conv3's raw-1 kernels run
+// the 16-row tiles as 8 waves of 8 rows x 16 px (MI = 8 halves the weight-fragment traffic per MFMA against
+// 4-row waves) and the 4-wave 8-row tiles as one row of 4 waves, each with half the channel tiles per wave
+static ConvTile conv_tile(const ConvCfg& c, bool conv3) {
+  if (conv3 && c.raw == 1 && c.w4) return {1, 4, c.ntn / 2, 8, 1};
+  if (conv3 && c.raw == 1 && c.wm == 4) return {2, 4, c.ntn / 2, 8, 1};
+  return {c.wm, c.wn, c.ntn, 4, c.raw};
+}
+
+#define CONV_TILE_IS(WM, WN, NTN, MI) (t.wm == WM && t.wn == WN && t.ntn == NTN && t.mi == MI)
+
 template <typename T, int KS, int RAW>
-static int dispatch_cfg(const unet_conv_desc* d, const ConvCfg& c, hipStream_t st) {
-  if (c.wm == 2 && c.wn == 2 && c.ntn == 1) return launch_conv2<T, KS, 2, 2, 1, RAW>(d, st);
-  if (c.wm == 4 && c.wn == 2 && c.ntn == 2) return launch_conv2<T, KS, 4, 2, 2, RAW>(d, st);
-  if (c.wm == 2 && c.wn == 2 && c.ntn == 2) return launch_conv2<T, KS, 2, 2, 2, RAW>(d, st);
-  if (c.wm == 4 && c.wn == 2 && c.ntn == 4) return launch_conv2<T, KS, 4, 2, 4, RAW>(d, st);
+static int dispatch_cfg(const unet_conv_desc* d, const ConvTile& t, hipStream_t st) {
+  if (CONV_TILE_IS(2, 2, 1, 4)) return launch_conv2<T, KS, 2, 2, 1, RAW>(d, st);
+  if (CONV_TILE_IS(4, 2, 2, 4)) return launch_conv2<T, KS, 4, 2, 2, RAW>(d, st);
+  if (CONV_TILE_IS(2, 2, 2, 4)) return launch_conv2<T, KS, 2, 2, 2, RAW>(d, st);
+  if (CONV_TILE_IS(4, 2, 4, 4)) return launch_conv2<T, KS, 4, 2, 4, RAW>(d, st);
   return launch_conv2<T, KS, 2, 4, 2, RAW>(d, st);
 }
 
-#include "conv3_body.inc"
+template <typename T>
+static int dispatch_conv2(const unet_conv_desc* d, const ConvTile& t, hipStream_t st) {
+  if (d->ksize == 3) return t.raw == 4 ? dispatch_cfg<T, 3, 4>(d, t, st) : dispatch_cfg<T, 3, 1>(d, t, st);
+  return t.raw == 4 ? dispatch_cfg<T, 1, 4>(d, t, st) : dispatch_cfg<T, 1, 1>(d, t, st);
+}
 
-template <typename T> int dispatch_generic(const unet_conv_desc* d, hipStream_t st);
-bool conv5_eligible(const unet_conv_desc* d);   // conv5.hip: the LDS-DMA 3x3 path
-bool conv5_serves(const unet_conv_desc* d);     // conv5.hip: eligible, or small enough for its split-K form
-size_t conv5_workspace(const unet_conv_desc* d);
-bool conv5_act_out_ok(const unet_conv_desc* d);
-int pack_tiles_launch(int dtype, int count, const unet_pack_job* jobs, hipStream_t st);   // pack.hip
-int conv5_run(const unet_conv_desc* d, hipStream_t st);
-int conv5_stats_rows(const unet_conv_desc* d);
-int conv5_variant(const unet_conv_desc* d, char* buf, int len);
-bool smallcin_conv_ok(const unet_conv_desc* d);  // smallcin.hip
-bool pw_conv_ok(const unet_conv_desc* d);        // pw.hip
-int pw_conv_rows(const unet_conv_desc* d);
-int pw_conv(const unet_conv_desc* d, hipStream_t st);
-int pw_conv_variant(const unet_conv_desc* d, char* buf, int len);
-int smallcin_rows(long long P);
-int smallcin_stats_rows(const unet_conv_desc* d);
-bool smallcin_is_mfma(const unet_conv_desc* d);
-int smallcin_conv(const unet_conv_desc* d, hipStream_t st);
+#include "conv3_body.inc"
 
 // the pipelined kernel needs every source channel vector to be one aligned 16-byte load, and every
 // source tensor addressable with 32-bit byte offsets
@@ -513,18 +511,36 @@ static bool fast_eligible(const unet_conv_desc* d) {
   return true;
 }
 
-template <typename T>
-static int dispatch_conv(const unet_conv_desc* d, hipStream_t st) {
-  if (!fast_eligible(d)) return dispatch_generic<T>(d, st);
-  if constexpr (sizeof(T) == 2) {
-    if (conv5_serves(d)) return conv5_run(d, st);
+// the one place that chooses d's kernel family, in priority order: smallcin, pw, generic (sources the pipelined
+// kernels cannot load), the conv5 forms (16-bit), conv3, conv2.  The split-K form is chosen only with a
+// non-null d->workspace; r.c5.workspace sizes it from the shape either way.
+ConvRoute conv_route(const unet_conv_desc* d) {
+  ConvRoute r{};
+  if (smallcin_conv_ok(d)) {
+    r.path = CONV_SMALLCIN;
+    r.stats_rows = smallcin_stats_rows(d);
+  } else if (pw_conv_ok(d)) {
+    r.path = CONV_PW;
+    r.stats_rows = pw_conv_rows(d);
+  } else if (!fast_eligible(d)) {
+    r.path = CONV_GENERIC;
+    r.stats_rows = d->N * cdiv(d->W, CTW) * cdiv(d->H, 8);
+  } else {
+    if (d->dtype != UNET_F32) r.c5 = conv5_route(d);
+    if (r.c5.form != C5_NONE) {
+      r.path = r.c5.form == C5_WIDE ? CONV_CONV5W : r.c5.form == C5_PLAIN ? CONV_CONV5 : CONV_CONV5_SPLITK;
+      r.stats_rows = r.c5.stats_rows;
+      r.bnb_in_epilogue = true;
+    } else {
+      const bool c3 = conv3_eligible(d);
+      r.path = c3 ? CONV_CONV3 : CONV_CONV2;
+      r.tile = conv_tile(pick_cfg(d), c3);
+      r.stats_rows = d->N * cdiv(d->W, CTW) * cdiv(d->H, r.tile.wm * r.tile.mi);
+      r.bnb_in_epilogue = c3 && conv3_bnb_tile(r.tile);
+    }
   }
-  const ConvCfg c = pick_cfg(d);
-  if constexpr (sizeof(T) == 2) {
-    if (conv3_eligible(d)) return dispatch_conv3<T>(d, c, st);
-  }
-  if (d->ksize == 3) return c.raw == 4 ? dispatch_cfg<T, 3, 4>(d, c, st) : dispatch_cfg<T, 3, 1>(d, c, st);
-  return c.raw == 4 ? dispatch_cfg<T, 1, 4>(d, c, st) : dispatch_cfg<T, 1, 1>(d, c, st);
+  if (d->bnb_y && !r.bnb_in_epilogue) r.stats_rows = unet_bn_bwd_reduce_rows((long long)d->N * d->H * d->W, d->Cout);
+  return r;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -598,60 +614,31 @@ using namespace unet;
 
 extern "C" {
 
-static const char* tname(int dtype) { return dtype == UNET_BF16 ? "bf16" : dtype == UNET_F16 ? "fp16" : "fp32"; }
-
 int unet_conv_mtiles(int N, int H, int W) { return N * cdiv(W, CTW) * cdiv(H, 8); }
 
-// does unet_conv reduce d's bnb_* sums in the conv epilogue (rows = the conv's M tiles)?
-static bool bnb_in_epilogue(const unet_conv_desc* d) {
-  if (smallcin_conv_ok(d) || pw_conv_ok(d) || !fast_eligible(d) || d->dtype == UNET_F32) return false;
-  if (conv5_serves(d)) return true;
-  return conv3_bnb_tile(d, pick_cfg(d));
-}
+// the query entry points read conv_route's answer and decide nothing themselves
+int unet_conv_stats_rows(const unet_conv_desc* d) { return conv_route(d).stats_rows; }
 
-int unet_conv_stats_rows(const unet_conv_desc* d) {
-  if (d->bnb_y && !bnb_in_epilogue(d)) return unet_bn_bwd_reduce_rows((long long)d->N * d->H * d->W, d->Cout);
-  if (smallcin_conv_ok(d)) return smallcin_stats_rows(d);
-  if (pw_conv_ok(d)) return pw_conv_rows(d);
-  if (!fast_eligible(d)) return d->N * cdiv(d->W, CTW) * cdiv(d->H, 8);
-  if (d->dtype != UNET_F32 && conv5_serves(d)) return conv5_stats_rows(d);
-  const ConvCfg c = pick_cfg(d);
-  return d->N * cdiv(d->W, CTW) * cdiv(d->H, 4 * c.wm);
-}
+size_t unet_conv_workspace(const unet_conv_desc* d) { return d ? conv_route(d).c5.workspace : 0; }
 
-size_t unet_conv_workspace(const unet_conv_desc* d) {
-  if (!d || smallcin_conv_ok(d) || pw_conv_ok(d) || !fast_eligible(d) || d->dtype == UNET_F32) return 0;
-  return conv5_workspace(d);
-}
-
-int unet_conv_act_out_ok(const unet_conv_desc* d) { return d && conv5_act_out_ok(d) ? 1 : 0; }
+int unet_conv_act_out_ok(const unet_conv_desc* d) { return d && conv_route(d).c5.act_out_ok ? 1 : 0; }
 
 int unet_conv_variant(const unet_conv_desc* d, char* buf, int len) {
-  if (smallcin_conv_ok(d)) {
-    snprintf(buf, len, smallcin_is_mfma(d) ? "smallcin_fwd_mfma_kernel<%s>" : "smallcin_fwd_kernel<%s>", tname(d->dtype));
-    return 0;
+  const ConvRoute r = conv_route(d);
+  const ConvTile& t = r.tile;
+  const char* tn = dtype_name(d->dtype);
+  switch (r.path) {
+    case CONV_SMALLCIN:
+      snprintf(buf, len, smallcin_is_mfma(d) ? "smallcin_fwd_mfma_kernel<%s>" : "smallcin_fwd_kernel<%s>", tn);
+      break;
+    case CONV_PW: return pw_conv_variant(d, buf, len);
+    case CONV_GENERIC: snprintf(buf, len, "conv_generic_kernel<%s,%d,%d>", tn, d->ksize, d->Cout <= 32 ? 32 : 64); break;
+    case CONV_CONV5W: snprintf(buf, len, r.c5.mi == 4 ? "conv5w_kernel<%s,4>" : "conv5w_kernel<%s>", tn); break;
+    case CONV_CONV5: snprintf(buf, len, "conv5_kernel<%s,%d>", tn, r.c5.mi); break;
+    case CONV_CONV5_SPLITK: snprintf(buf, len, "conv5_kernel<%s,%d>+splitk%d", tn, r.c5.mi, r.c5.splitk); break;
+    case CONV_CONV3: snprintf(buf, len, "conv3_kernel<%s,3,%d,%d,%d,%d,%d>", tn, t.wm, t.wn, t.ntn, t.mi, t.raw); break;
+    case CONV_CONV2: snprintf(buf, len, "conv2_kernel<%s,%d,%d,%d,%d,%d>", tn, d->ksize, t.wm, t.wn, t.ntn, t.raw); break;
   }
-  if (pw_conv_ok(d)) return pw_conv_variant(d, buf, len);
-  if (!fast_eligible(d)) {
-    snprintf(buf, len, "conv_generic_kernel<%s,%d,%d>", tname(d->dtype), d->ksize,
-             d->Cout <= 32 ? 32 : 64);
-    return 0;
-  }
-  if (d->dtype != UNET_F32 && conv5_serves(d)) return conv5_variant(d, buf, len);
-  const ConvCfg c = pick_cfg(d);
-  if (conv3_eligible(d)) {
-    // the (wm, wn, ntn) block tile of pick_cfg; 16-row tiles run as MI=8 waves (dispatch_conv3)
-    if (c.w4) {
-      snprintf(buf, len, "conv3_kernel<%s,3,1,4,%d,8,1>", tname(d->dtype), c.ntn / 2);
-      return 0;
-    }
-    const bool mi8 = c.raw == 1 && c.wm == 4 && (c.ntn == 4 || c.ntn == 2);
-    snprintf(buf, len, "conv3_kernel<%s,3,%d,%d,%d,%d,%d>", tname(d->dtype), mi8 ? 2 : c.wm, mi8 ? 4 : c.wn, mi8 ? c.ntn / 2 : c.ntn,
-             mi8 ? 8 : 4, c.raw);
-    return 0;
-  }
-  snprintf(buf, len, "conv2_kernel<%s,%d,%d,%d,%d,%d>", tname(d->dtype), d->ksize, c.wm, c.wn,
-           c.ntn, c.raw);
   return 0;
 }
 
@@ -714,14 +701,6 @@ int unet_pack_weight(int dtype, const float* w, void* packed, int Cout, int Cin,
   return check_launch("pack_weight");
 }
 
-static int validate_src(const unet_src& s) {
-  if (s.kind < 0 || s.kind > UNET_SRC_UP_PLAIN || !s.data || s.C <= 0) return 0;
-  if ((s.kind == UNET_SRC_ACT || s.kind == UNET_SRC_POOL_ACT || s.kind == UNET_SRC_UP_ACT) && (!s.scale || !s.shift))
-    return 0;
-  if (s.gate_p && !s.gate_ab) return 0;
-  return 1;
-}
-
 int unet_conv(const unet_conv_desc* d, void* stream) {
   if (!d || d->N <= 0 || d->H <= 0 || d->W <= 0 || d->Cin <= 0 || d->Cout <= 0 || !d->weight || !d->out ||
       (d->ksize != 1 && d->ksize != 3) || d->nsrc < 1 || d->nsrc > 2) {
@@ -766,17 +745,25 @@ int unet_conv(const unet_conv_desc* d, void* stream) {
     set_error("unet_conv: bad dtype");
     return UNET_ERR_ARG;
   }
-  if (d->act_out && !conv5_act_out_ok(d)) {
+  const ConvRoute r = conv_route(d);
+  if (d->act_out && !r.c5.act_out_ok) {
     set_error("unet_conv: act_out is served for y-mode BN-activation sources on the conv5 path only "
               "(ask unet_conv_act_out_ok)");
     return UNET_ERR_ARG;
   }
   hipStream_t st = (hipStream_t)stream;
-  int rc;
-  if (smallcin_conv_ok(d)) rc = smallcin_conv(d, st);
-  else if (pw_conv_ok(d)) rc = pw_conv(d, st);
-  else rc = UNET_DISPATCH_T(d->dtype, dispatch_conv<T>(d, st));
-  if (rc || !d->bnb_stats || bnb_in_epilogue(d)) return rc;
+  int rc = UNET_ERR_ARG;
+  switch (r.path) {
+    case CONV_SMALLCIN: rc = smallcin_conv(d, st); break;
+    case CONV_PW: rc = pw_conv(d, st); break;
+    case CONV_GENERIC: rc = conv_generic(d, st); break;
+    case CONV_CONV5W:
+    case CONV_CONV5:
+    case CONV_CONV5_SPLITK: rc = conv5_run(d, r.c5, st); break;
+    case CONV_CONV3: rc = d->dtype == UNET_F16 ? dispatch_conv3<f16>(d, r.tile, st) : dispatch_conv3<bf16>(d, r.tile, st); break;
+    case CONV_CONV2: rc = UNET_DISPATCH_T(d->dtype, dispatch_conv2<T>(d, r.tile, st)); break;
+  }
+  if (rc || !d->bnb_stats || r.bnb_in_epilogue) return rc;
   // the other paths: the separate BatchNorm-backward reduction over the stored gradient
   return unet_bn_bwd_reduce(d->dtype, d->dtype, (long long)d->N * d->H * d->W, d->Cout, d->out, d->bnb_y,
                             d->bnb_scale, d->bnb_shift, d->bnb_relu, d->bnb_mean, d->bnb_invstd, d->bnb_stats,

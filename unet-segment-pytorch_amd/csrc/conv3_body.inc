@@ -491,24 +491,26 @@ static bool conv3_eligible(const unet_conv_desc* d) {
   return true;
 }
 
+#define CONV3_TILE(WM, WN, NTN, MI) \
+  if (CONV_TILE_IS(WM, WN, NTN, MI)) return launch_conv3<T, WM, WN, NTN, MI, 1, 0, OM, SK>(d, st)
+
 template <typename T, int OM, int SK>
-static int dispatch_conv3_raw1(const unet_conv_desc* d, const ConvCfg& c, hipStream_t st) {
-  if constexpr (OM == UNET_OUT_Y || OM == OM_Y_BNB) {
-    if (c.w4)
-      return c.ntn == 4 ? launch_conv3<T, 1, 4, 2, 8, 1, 0, OM, SK>(d, st) : launch_conv3<T, 1, 4, 1, 8, 1, 0, OM, SK>(d, st);
+static int dispatch_conv3_raw1(const unet_conv_desc* d, const ConvTile& t, hipStream_t st) {
+  if constexpr (OM == UNET_OUT_Y || OM == OM_Y_BNB) {   // the 4-wave 8-row tiles (pick_cfg: y epilogues only)
+    CONV3_TILE(1, 4, 2, 8);
+    CONV3_TILE(1, 4, 1, 8);
   }
-  if (c.wm == 2 && c.wn == 2 && c.ntn == 1) return launch_conv3<T, 2, 2, 1, 4, 1, 0, OM, SK>(d, st);
-  if (c.wm == 4 && c.wn == 2 && c.ntn == 2) return launch_conv3<T, 2, 4, 1, 8, 1, 0, OM, SK>(d, st);
-  if (c.wm == 2 && c.wn == 2 && c.ntn == 2) return launch_conv3<T, 2, 2, 2, 4, 1, 0, OM, SK>(d, st);
-  if (c.wm == 4 && c.wn == 2 && c.ntn == 4) return launch_conv3<T, 2, 4, 2, 8, 1, 0, OM, SK>(d, st);
+  CONV3_TILE(2, 2, 1, 4);
+  CONV3_TILE(2, 4, 1, 8);
+  CONV3_TILE(2, 2, 2, 4);
+  CONV3_TILE(2, 4, 2, 8);
   return launch_conv3<T, 2, 4, 2, 4, 1, 0, OM, SK>(d, st);
 }
+#undef CONV3_TILE
 
 // the dgrad y epilogue reduces the BatchNorm-backward sums itself (bnb_*) on the 16-channel wave tiles
 // (Dᵀ epilogue, 8-byte y prefetch per lane); the other tiles leave them to unet_bn_bwd_reduce
-static bool conv3_bnb_tile(const unet_conv_desc* d, const ConvCfg& c) {
-  return conv3_eligible(d) && c.raw == 1 && (c.ntn == 1 || (c.ntn == 2 && (c.w4 || (c.wm == 4 && c.wn == 2))));
-}
+static bool conv3_bnb_tile(const ConvTile& t) { return t.raw == 1 && t.ntn == 1; }
 
 // the SK specialisation a raw-1 descriptor can use (conv3_eligible already holds)
 static int conv3_source_kinds(const unet_conv_desc* d) {
@@ -522,15 +524,14 @@ static int conv3_source_kinds(const unet_conv_desc* d) {
 }
 
 template <typename T>
-static int dispatch_conv3(const unet_conv_desc* d, const ConvCfg& c, hipStream_t st) {
-  if (c.raw == 4 && d->out_mode == UNET_OUT_Y) {
-    if (c.wm == 4 && c.wn == 2 && c.ntn == 2) return launch_conv3<T, 4, 2, 2, 4, 4, 0, UNET_OUT_Y>(d, st);
-    if (c.wm == 2 && c.wn == 2 && c.ntn == 1) return launch_conv3<T, 2, 2, 1, 4, 4, 0, UNET_OUT_Y>(d, st);
-    if (c.wm == 2 && c.wn == 2 && c.ntn == 2) return launch_conv3<T, 2, 2, 2, 4, 4, 0, UNET_OUT_Y>(d, st);
+static int dispatch_conv3(const unet_conv_desc* d, const ConvTile& t, hipStream_t st) {
+  if (t.raw == 4 && d->out_mode == UNET_OUT_Y) {
+    if (CONV_TILE_IS(4, 2, 2, 4)) return launch_conv3<T, 4, 2, 2, 4, 4, 0, UNET_OUT_Y>(d, st);
+    if (CONV_TILE_IS(2, 2, 1, 4)) return launch_conv3<T, 2, 2, 1, 4, 4, 0, UNET_OUT_Y>(d, st);
+    if (CONV_TILE_IS(2, 2, 2, 4)) return launch_conv3<T, 2, 2, 2, 4, 4, 0, UNET_OUT_Y>(d, st);
     return launch_conv3<T, 2, 4, 2, 4, 4, 0, UNET_OUT_Y>(d, st);
   }
-  // same block tiles as conv2's configurations; the 16-row tiles run as 8 waves of 8 rows x 16 px
-  // (MI = 8 halves the weight-fragment traffic per MFMA against 4-row waves).  The epilogue is
+  // the kernel tuples of conv_tile (conv.hip) over conv2's block tiles.  The epilogue is
   // specialised per output mode (y+stats / fp32 dgrad / pool backward): one mode's code stays small
   // enough to sit inside the persistent tile loop without spilling
   // measured (kernel-resource-usage, chunk loop rolled): the plain-source specialisation removes every
@@ -538,25 +539,24 @@ static int dispatch_conv3(const unet_conv_desc* d, const ConvCfg& c, hipStream_t
   // forward tiles over materialised inputs; the BN-activation ones lower the VGPR count of the 16-channel
   // (NTN = 1) wave tiles, but on the 32-channel ones they let the scheduler hoist more and spill more, so
   // those keep the run-time switch
-  const bool ntn1 = c.ntn == 1 || (c.ntn == 2 && (c.w4 || (c.wm == 4 && c.wn == 2)));  // kernel NTN == 1
   int sk = conv3_source_kinds(d);
-  if (!ntn1 && sk != SK_PLAIN) sk = SK_ANY;
-  if (d->out_mode == UNET_OUT_Y && d->bnb_stats && conv3_bnb_tile(d, c))   // a dgrad: plain dy source
-    return sk == SK_PLAIN ? dispatch_conv3_raw1<T, OM_Y_BNB, SK_PLAIN>(d, c, st)
-                          : dispatch_conv3_raw1<T, OM_Y_BNB, SK_ANY>(d, c, st);
+  if (t.ntn != 1 && sk != SK_PLAIN) sk = SK_ANY;
+  if (d->out_mode == UNET_OUT_Y && d->bnb_stats && conv3_bnb_tile(t))   // a dgrad: plain dy source
+    return sk == SK_PLAIN ? dispatch_conv3_raw1<T, OM_Y_BNB, SK_PLAIN>(d, t, st)
+                          : dispatch_conv3_raw1<T, OM_Y_BNB, SK_ANY>(d, t, st);
   if (d->out_mode == UNET_OUT_Y) {
-    if (sk == SK_PLAIN) return dispatch_conv3_raw1<T, UNET_OUT_Y, SK_PLAIN>(d, c, st);
-    if (sk == SK_ACT_PLAIN) return dispatch_conv3_raw1<T, UNET_OUT_Y, SK_ACT_PLAIN>(d, c, st);
-    if (sk == SK_ACT) return dispatch_conv3_raw1<T, UNET_OUT_Y, SK_ACT>(d, c, st);
-    return dispatch_conv3_raw1<T, UNET_OUT_Y, SK_ANY>(d, c, st);
+    if (sk == SK_PLAIN) return dispatch_conv3_raw1<T, UNET_OUT_Y, SK_PLAIN>(d, t, st);
+    if (sk == SK_ACT_PLAIN) return dispatch_conv3_raw1<T, UNET_OUT_Y, SK_ACT_PLAIN>(d, t, st);
+    if (sk == SK_ACT) return dispatch_conv3_raw1<T, UNET_OUT_Y, SK_ACT>(d, t, st);
+    return dispatch_conv3_raw1<T, UNET_OUT_Y, SK_ANY>(d, t, st);
   }
   // the gradient modes read the plain output gradient dy
   if (d->out_mode == UNET_OUT_F32)
-    return sk == SK_PLAIN ? dispatch_conv3_raw1<T, UNET_OUT_F32, SK_PLAIN>(d, c, st)
-                          : dispatch_conv3_raw1<T, UNET_OUT_F32, SK_ANY>(d, c, st);
+    return sk == SK_PLAIN ? dispatch_conv3_raw1<T, UNET_OUT_F32, SK_PLAIN>(d, t, st)
+                          : dispatch_conv3_raw1<T, UNET_OUT_F32, SK_ANY>(d, t, st);
   if (d->out_mode == UNET_OUT_POOL_BWD)
-    return sk == SK_PLAIN ? dispatch_conv3_raw1<T, UNET_OUT_POOL_BWD, SK_PLAIN>(d, c, st)
-                          : dispatch_conv3_raw1<T, UNET_OUT_POOL_BWD, SK_ANY>(d, c, st);
+    return sk == SK_PLAIN ? dispatch_conv3_raw1<T, UNET_OUT_POOL_BWD, SK_PLAIN>(d, t, st)
+                          : dispatch_conv3_raw1<T, UNET_OUT_POOL_BWD, SK_ANY>(d, t, st);
   set_error("unet_conv: output mode not served by the 3x3 path");
   return UNET_ERR_UNSUPPORTED;
 }

@@ -32,14 +32,9 @@
 // reduced once (one partial row per wave row group: [.. gridDim.x * 4 ..]).
 #include "conv_mfma32.h"
 #include "lds_dma.h"
+#include "paths.h"
 
 namespace unet {
-
-// conv5w.hip: the 128-output-channel form (round 6), preferred wherever it serves
-bool conv5w_ok(const unet_conv_desc* d);
-int conv5w_stats_rows(const unet_conv_desc* d);
-int conv5w_variant(const unet_conv_desc* d, char* buf, int len);
-int conv5w_run(const unet_conv_desc* d, int prio, hipStream_t st);
 
 constexpr int C5_W = 32, C5_HW = 34;     // tile width, halo width (pixels)
 constexpr int C5_WM = 4;                 // wave row groups of a workgroup tile
@@ -988,55 +983,6 @@ static bool conv5_shape_ok(const unet_conv_desc* d) {
   return true;
 }
 
-bool conv5_eligible(const unet_conv_desc* d) {
-  const int mode = conv5_mode();
-  if (mode == 0) return false;
-  // default: every 16-bit y output (forward and the middle-activation dgrads) and the fp32 dgrads of <= 64
-  // channels — per layer conv5 measured 0-31 % faster there (the 512^2 64-channel layers 14-31 %); the
-  // wider fp32 dgrads stay on conv3, whose tiles measured 5-20 % faster (profiles/r03_layerprof_*.txt)
-  // (the small maps' MI = 2 form serves the wide fp32 dgrads too: conv3 there is a 64- or 128-workgroup launch)
-  if (!conv5_shape_ok(d)) return false;
-  const int mi = conv5_mi(d);
-  if (mode == 2 && d->out_mode == UNET_OUT_F32 && d->Cout > C5_BN && mi == C5_MI) return false;
-  const long long work = conv5_mtiles(d, mi) * cdiv(d->Cout, C5_BN);
-  return work >= 256;
-}
-
-// ---- split-K over the input channels for maps whose 16 x 32 x 64 tiles do not fill the chip (round 5,
-// VERDICT r04 item 4: the 32^2 512 -> 512 down4 layers ran on conv3 at 12-15 % of peak with 64 tiles of work):
-// S = the smallest power of two with tiles x S >= 256 (<= 8), each split >= 2 chunks; the partial sums go to
-// S fp32 slabs in d->workspace and conv5_splitk_finish_kernel adds them in slab order (deterministic) and applies
-// the real epilogue (y + BN partial sums, y + BN-backward sums, or fp32 with split / accumulation).
-// UNET_CONV5_SPLIT=0 turns it off (A/B).
-// the split count of d's shape (unet_conv_workspace sizes the slabs from it, whatever d->workspace holds)
-static int conv5_splitk_shape(const unet_conv_desc* d) {
-  const char* e = getenv("UNET_CONV5_SPLIT");   // read per call (tests flip it)
-  const int on = e ? atoi(e) : 1;
-  if (!on || conv5_mode() == 0 || d->act_out || !conv5_shape_ok(d) || conv5w_ok(d)) return 1;
-  if (d->Cout > 1024 || (d->Cout & (d->Cout - 1))) return 1;     // the finisher's channel-vector layout
-  // a slab is addressed by one buffer resource (32-bit range): the kernel's counted fp32 stores need it
-  if ((double)d->N * d->H * d->W * d->Cout * 4 >= (double)OOB) return 1;
-  const long long work = conv5_mtiles(d, conv5_mi(d)) * cdiv(d->Cout, C5_BN);
-  if (work >= 256) return 1;
-  const int nch = cdiv(d->Cin, 16);
-  int S = 1;
-  while (work * S < 256 && S < 8 && nch % (2 * S) == 0 && nch / (2 * S) >= 2) S *= 2;
-  return S;
-}
-
-// the split count unet_conv runs d with: the shape's, if the caller passed a workspace (a
-// descriptor without one — e.g. zero-initialised by a C caller — runs the unsplit form, as before round 5)
-int conv5_splitk(const unet_conv_desc* d) { return d->workspace ? conv5_splitk_shape(d) : 1; }
-
-bool conv5_serves(const unet_conv_desc* d) {
-  return (conv5_mode() != 0 && conv5w_ok(d)) || conv5_eligible(d) || conv5_splitk(d) > 1;
-}
-
-size_t conv5_workspace(const unet_conv_desc* d) {
-  const int S = conv5_eligible(d) ? 1 : conv5_splitk_shape(d);
-  return S > 1 ? (size_t)S * d->N * d->H * d->W * d->Cout * sizeof(float) : 0;
-}
-
 // the finisher: 256 threads = CV channel vectors (4 channels) x R pixel lanes, FIN_TRIPS pixels per lane
 static int fin_rows(const unet_conv_desc* d) {
   const int R = 256 / (d->Cout / 4);
@@ -1045,27 +991,71 @@ static int fin_rows(const unet_conv_desc* d) {
   return (int)(rows < 1 ? 1 : rows);
 }
 
-int conv5_stats_rows(const unet_conv_desc* d) {
-  if (conv5_mode() != 0 && conv5w_ok(d)) return conv5w_stats_rows(d);
-  if (!conv5_eligible(d) && conv5_splitk(d) > 1) return fin_rows(d);
-  return conv5_gx(d, conv5_mi(d)) * C5_WM;
+// ---- split-K over the input channels for maps whose 16 x 32 x 64 tiles do not fill the chip (round 5,
+// VERDICT r04 item 4: the 32^2 512 -> 512 down4 layers ran on conv3 at 12-15 % of peak with 64 tiles of work):
+// S = the smallest power of two with tiles x S >= 256 (<= 8), each split >= 2 chunks; the partial sums go to
+// S fp32 slabs in d->workspace and conv5_splitk_finish_kernel adds them in slab order (deterministic) and applies
+// the real epilogue (y + BN partial sums, y + BN-backward sums, or fp32 with split / accumulation).
+// UNET_CONV5_SPLIT=0 turns it off (A/B).
+// the split count of a shape conv5_shape_ok admits, with `work` (< 256) workgroup tiles
+static int conv5_splitk_shape(const unet_conv_desc* d, long long work) {
+  const char* e = getenv("UNET_CONV5_SPLIT");   // read per call (tests flip it)
+  const int on = e ? atoi(e) : 1;
+  if (!on || d->act_out) return 1;
+  if (d->Cout > 1024 || (d->Cout & (d->Cout - 1))) return 1;     // the finisher's channel-vector layout
+  // a slab is addressed by one buffer resource (32-bit range): the kernel's counted fp32 stores need it
+  if ((double)d->N * d->H * d->W * d->Cout * 4 >= (double)OOB) return 1;
+  const int nch = cdiv(d->Cin, 16);
+  int S = 1;
+  while (work * S < 256 && S < 8 && nch % (2 * S) == 0 && nch / (2 * S) >= 2) S *= 2;
+  return S;
 }
 
-// can the forward write src[0]'s transformed input to act_out (the y-mode BN-activation kernel serves d)?
-bool conv5_act_out_ok(const unet_conv_desc* d) {
-  if (conv5_mode() != 0 && conv5w_ok(d))
-    return d->out_mode == UNET_OUT_Y && !d->bnb_stats && d->src[0].kind == UNET_SRC_ACT;
-  return conv5_eligible(d) && d->out_mode == UNET_OUT_Y && !d->bnb_stats && d->src[0].kind == UNET_SRC_ACT &&
-         d->src[0].C % 16 == 0;
+// the 64-channel forms (mode: conv5_mode()): plain where the tiles fill the chip, split-K where they do not and
+// the caller passed a workspace (a descriptor without one — e.g. zero-initialised by a C caller —
+// runs the unsplit kernels, as before round 5); r.workspace sizes the slabs from the shape either way
+static Conv5Route conv5_narrow_route(const unet_conv_desc* d, int mode) {
+  Conv5Route r;
+  if (mode == 0 || !conv5_shape_ok(d)) return r;
+  r.mi = conv5_mi(d);
+  const long long work = conv5_mtiles(d, r.mi) * cdiv(d->Cout, C5_BN);
+  if (work >= 256) {
+    // default: every 16-bit y output (forward and the middle-activation dgrads) and the fp32 dgrads of <= 64
+    // channels — per layer conv5 measured 0-31 % faster there (the 512^2 64-channel layers 14-31 %); the
+    // wider fp32 dgrads stay on conv3, whose tiles measured 5-20 % faster (profiles/r03_layerprof_*.txt)
+    // (the small maps' MI = 2 form serves the wide fp32 dgrads too: conv3 there is a 64- or 128-workgroup launch)
+    if (mode == 2 && d->out_mode == UNET_OUT_F32 && d->Cout > C5_BN && r.mi == C5_MI) return r;
+    r.form = C5_PLAIN;
+    r.stats_rows = conv5_gx(d, r.mi) * C5_WM;
+    // the y-mode BN-activation kernel can write src[0]'s transformed input
+    r.act_out_ok = d->out_mode == UNET_OUT_Y && !d->bnb_stats && d->src[0].kind == UNET_SRC_ACT && d->src[0].C % 16 == 0;
+    return r;
+  }
+  r.splitk = conv5_splitk_shape(d, work);
+  if (r.splitk > 1) {
+    r.workspace = (size_t)r.splitk * d->N * d->H * d->W * d->Cout * sizeof(float);
+    if (d->workspace) {
+      r.form = C5_SPLITK;
+      r.stats_rows = fin_rows(d);
+    }
+  }
+  return r;
 }
 
-int conv5_variant(const unet_conv_desc* d, char* buf, int len) {
-  if (conv5_mode() != 0 && conv5w_ok(d)) return conv5w_variant(d, buf, len);
-  const int S = conv5_eligible(d) ? 1 : conv5_splitk(d);
-  const int mi = conv5_mi(d);
-  if (S > 1) snprintf(buf, len, "conv5_kernel<%s,%d>+splitk%d", d->dtype == UNET_F16 ? "fp16" : "bf16", mi, S);
-  else snprintf(buf, len, "conv5_kernel<%s,%d>", d->dtype == UNET_F16 ? "fp16" : "bf16", mi);
-  return 0;
+// the one classifier of the conv5 family: conv5w (the 128-output-channel form, round 6) wherever it serves,
+// else the 64-channel forms
+Conv5Route conv5_route(const unet_conv_desc* d) {
+  const int mode = conv5_mode();
+  int wmi;
+  if (mode != 0 && conv5w_ok(d, &wmi)) {
+    Conv5Route r;
+    r.form = C5_WIDE;
+    r.mi = wmi;
+    r.stats_rows = conv5w_stats_rows(d, wmi);
+    r.act_out_ok = d->out_mode == UNET_OUT_Y && !d->bnb_stats && d->src[0].kind == UNET_SRC_ACT;
+    return r;
+  }
+  return conv5_narrow_route(d, mode);
 }
 
 // PIPE: the column-ahead operand reads (per layer 5-9 % faster: 117 -> 108 us on the 512^2 64->64 forward,
@@ -1090,9 +1080,9 @@ static int launch5_mi(const unet_conv_desc* d, hipStream_t st) {
   return check_launch("conv5");
 }
 template <typename T, int OM, int SK, int GATE, int ABL = 0, int PIPE_ = -1>
-static int launch5(const unet_conv_desc* d, hipStream_t st) {
+static int launch5(const unet_conv_desc* d, int mi, hipStream_t st) {
   if constexpr (ABL == 0) {
-    if (conv5_mi(d) == C5_MI_S) return launch5_mi<T, OM, SK, GATE, 0, PIPE_, C5_MI_S>(d, st);
+    if (mi == C5_MI_S) return launch5_mi<T, OM, SK, GATE, 0, PIPE_, C5_MI_S>(d, st);
   }
   return launch5_mi<T, OM, SK, GATE, ABL, PIPE_, C5_MI>(d, st);
 }
@@ -1105,7 +1095,7 @@ static void launch5_finish_m(const unet_conv_desc* d, int S, hipStream_t st) {
   else if (S == 4) hipLaunchKernelGGL((conv5_splitk_finish_kernel<T, MODE, 4>), dim3(rows), dim3(256), 0, st, *d, ws, rows);
   else hipLaunchKernelGGL((conv5_splitk_finish_kernel<T, MODE, 8>), dim3(rows), dim3(256), 0, st, *d, ws, rows);
 }
-// the finisher of a split-K conv (S in {2, 4, 8}: conv5_splitk)
+// the finisher of a split-K conv (S in {2, 4, 8}: conv5_splitk_shape)
 template <typename T>
 static int launch5_finish(const unet_conv_desc* d, int S, hipStream_t st) {
   if (d->out_mode == UNET_OUT_F32) launch5_finish_m<T, 2>(d, S, st);
@@ -1118,7 +1108,7 @@ static int launch5_finish(const unet_conv_desc* d, int S, hipStream_t st) {
 template <typename T, int SK, int GATE, int MI>
 static int launch5_split_mi(const unet_conv_desc* d, int S, hipStream_t st) {
   constexpr int TH = C5_WM * MI;
-  if (!d->workspace || S < 2 || (double)d->N * d->H * d->W * d->Cout * 4 >= (double)OOB) {   // (conv5_splitk)
+  if (!d->workspace || S < 2 || (double)d->N * d->H * d->W * d->Cout * 4 >= (double)OOB) {   // (conv5_narrow_route)
     set_error("unet_conv: split-K without a workspace or past a slab's 32-bit range");
     return UNET_ERR_ARG;
   }
@@ -1141,71 +1131,70 @@ static int launch5_split_mi(const unet_conv_desc* d, int S, hipStream_t st) {
   return launch5_finish<T>(d, S, st);
 }
 template <typename T, int SK, int GATE>
-static int launch5_split(const unet_conv_desc* d, int S, hipStream_t st) {
-  return conv5_mi(d) == C5_MI_S ? launch5_split_mi<T, SK, GATE, C5_MI_S>(d, S, st) : launch5_split_mi<T, SK, GATE, C5_MI>(d, S, st);
+static int launch5_split(const unet_conv_desc* d, const Conv5Route& r, hipStream_t st) {
+  return r.mi == C5_MI_S ? launch5_split_mi<T, SK, GATE, C5_MI_S>(d, r.splitk, st)
+                         : launch5_split_mi<T, SK, GATE, C5_MI>(d, r.splitk, st);
 }
 
 // source kind of a descriptor: plain, one BN activation (gated or not), or a BN activation + a stored map.
 // The gradient epilogues (whose network sources are the stored dy) get the generic activation form only.
 template <typename T, int OM>
-static int dispatch5_om(const unet_conv_desc* d, hipStream_t st) {
+static int dispatch5_om(const unet_conv_desc* d, int mi, hipStream_t st) {
   const unet_src& s0 = d->src[0];
   const bool one = d->nsrc == 1 && s0.C % 16 == 0;
   if constexpr (OM == OM5_BNB) {   // UNET_C5_BNB_PIPE=0: the round-4 schedule of the dy dgrads (A/B)
     const char* e = getenv("UNET_C5_BNB_PIPE");
-    if (one && s0.kind != UNET_SRC_ACT && e && !atoi(e)) return launch5<T, OM, SK5_PLAIN1, 0, 0, 0>(d, st);
+    if (one && s0.kind != UNET_SRC_ACT && e && !atoi(e)) return launch5<T, OM, SK5_PLAIN1, 0, 0, 0>(d, mi, st);
   }
-  if (s0.kind != UNET_SRC_ACT) return one ? launch5<T, OM, SK5_PLAIN1, 0>(d, st) : launch5<T, OM, SK_PLAIN, 0>(d, st);
+  if (s0.kind != UNET_SRC_ACT) return one ? launch5<T, OM, SK5_PLAIN1, 0>(d, mi, st) : launch5<T, OM, SK_PLAIN, 0>(d, mi, st);
   const bool g = s0.gate_p != nullptr;
   if constexpr (OM == OM5_Y) {
-    if (one) return g ? launch5<T, OM, SK_ACT, 1>(d, st) : launch5<T, OM, SK_ACT, 0>(d, st);
+    if (one) return g ? launch5<T, OM, SK_ACT, 1>(d, mi, st) : launch5<T, OM, SK_ACT, 0>(d, mi, st);
   }
-  return g ? launch5<T, OM, SK_ACT_PLAIN, 1>(d, st) : launch5<T, OM, SK_ACT_PLAIN, 0>(d, st);
+  return g ? launch5<T, OM, SK_ACT_PLAIN, 1>(d, mi, st) : launch5<T, OM, SK_ACT_PLAIN, 0>(d, mi, st);
 }
 
 template <typename T>
-static int dispatch5(const unet_conv_desc* d, hipStream_t st) {
-  if (!conv5_eligible(d)) {
-    const int S = conv5_splitk(d);
+static int dispatch5(const unet_conv_desc* d, const Conv5Route& r, hipStream_t st) {
+  if (r.form == C5_SPLITK) {
     const unet_src& s0 = d->src[0];
     const bool one = d->nsrc == 1 && s0.C % 16 == 0;
     if (s0.kind != UNET_SRC_ACT)
-      return one ? launch5_split<T, SK5_PLAIN1, 0>(d, S, st) : launch5_split<T, SK_PLAIN, 0>(d, S, st);
-    if (one) return s0.gate_p ? launch5_split<T, SK_ACT, 1>(d, S, st) : launch5_split<T, SK_ACT, 0>(d, S, st);
-    return s0.gate_p ? launch5_split<T, SK_ACT_PLAIN, 1>(d, S, st) : launch5_split<T, SK_ACT_PLAIN, 0>(d, S, st);
+      return one ? launch5_split<T, SK5_PLAIN1, 0>(d, r, st) : launch5_split<T, SK_PLAIN, 0>(d, r, st);
+    if (one) return s0.gate_p ? launch5_split<T, SK_ACT, 1>(d, r, st) : launch5_split<T, SK_ACT, 0>(d, r, st);
+    return s0.gate_p ? launch5_split<T, SK_ACT_PLAIN, 1>(d, r, st) : launch5_split<T, SK_ACT_PLAIN, 0>(d, r, st);
   }
-  if (d->out_mode == UNET_OUT_F32) return dispatch5_om<T, OM5_F32>(d, st);
-  if (d->bnb_stats) return dispatch5_om<T, OM5_BNB>(d, st);
-  return dispatch5_om<T, OM5_Y>(d, st);
+  if (d->out_mode == UNET_OUT_F32) return dispatch5_om<T, OM5_F32>(d, r.mi, st);
+  if (d->bnb_stats) return dispatch5_om<T, OM5_BNB>(d, r.mi, st);
+  return dispatch5_om<T, OM5_Y>(d, r.mi, st);
 }
 
-int conv5_run(const unet_conv_desc* d, hipStream_t st) {
-  if (conv5_mode() != 0 && conv5w_ok(d)) return conv5w_run(d, conv5_prio(), st);
-  return d->dtype == UNET_F16 ? dispatch5<f16>(d, st) : dispatch5<bf16>(d, st);
+int conv5_run(const unet_conv_desc* d, const Conv5Route& r, hipStream_t st) {
+  if (r.form == C5_WIDE) return conv5w_run(d, r.mi, conv5_prio(), st);
+  return d->dtype == UNET_F16 ? dispatch5<f16>(d, r, st) : dispatch5<bf16>(d, r, st);
 }
 
 template <int SK, int GATE>
-static int abl5(const unet_conv_desc* d, int abl, hipStream_t st) {
+static int abl5(const unet_conv_desc* d, int mi, int abl, hipStream_t st) {
   switch (abl) {
-    case 0: return launch5<bf16, OM5_Y, SK, GATE, 0>(d, st);
-    case 1: return launch5<bf16, OM5_Y, SK, GATE, 1>(d, st);
-    case 2: return launch5<bf16, OM5_Y, SK, GATE, 2>(d, st);
-    case 3: return launch5<bf16, OM5_Y, SK, GATE, 3>(d, st);
-    case 4: return launch5<bf16, OM5_Y, SK, GATE, 4>(d, st);
-    case 8: return launch5<bf16, OM5_Y, SK, GATE, 8>(d, st);
-    case 7: return launch5<bf16, OM5_Y, SK, GATE, 7>(d, st);
-    case 15: return launch5<bf16, OM5_Y, SK, GATE, 15>(d, st);
-    case 16: return launch5<bf16, OM5_Y, SK, GATE, 16>(d, st);
-    case 31: return launch5<bf16, OM5_Y, SK, GATE, 31>(d, st);
+    case 0: return launch5<bf16, OM5_Y, SK, GATE, 0>(d, mi, st);
+    case 1: return launch5<bf16, OM5_Y, SK, GATE, 1>(d, mi, st);
+    case 2: return launch5<bf16, OM5_Y, SK, GATE, 2>(d, mi, st);
+    case 3: return launch5<bf16, OM5_Y, SK, GATE, 3>(d, mi, st);
+    case 4: return launch5<bf16, OM5_Y, SK, GATE, 4>(d, mi, st);
+    case 8: return launch5<bf16, OM5_Y, SK, GATE, 8>(d, mi, st);
+    case 7: return launch5<bf16, OM5_Y, SK, GATE, 7>(d, mi, st);
+    case 15: return launch5<bf16, OM5_Y, SK, GATE, 15>(d, mi, st);
+    case 16: return launch5<bf16, OM5_Y, SK, GATE, 16>(d, mi, st);
+    case 31: return launch5<bf16, OM5_Y, SK, GATE, 31>(d, mi, st);
   }
   return UNET_ERR_ARG;
 }
 
 // split-K ablations: the split kernel alone (ABL bits as above) or, abl < 0, the y + BN-stats finisher alone
 template <int SK, int MI>
-static int abl5_split_mi(const unet_conv_desc* d, int abl, hipStream_t st) {
+static int abl5_split_mi(const unet_conv_desc* d, int S, int abl, hipStream_t st) {
   constexpr int TH = C5_WM * MI;
-  const int S = conv5_splitk(d);
   const int tw = cdiv(d->W, C5_W), th = cdiv(d->H, TH), mt = d->N * tw * th, gy = cdiv(d->Cout, C5_BN);
   const int nch = cdiv(d->Cin, 16);
   if (S < 2 || !d->workspace) return UNET_ERR_ARG;
@@ -1239,8 +1228,8 @@ static int abl5_split_mi(const unet_conv_desc* d, int abl, hipStream_t st) {
   return check_launch("conv5 split (diag)");
 }
 template <int SK>
-static int abl5_split(const unet_conv_desc* d, int abl, hipStream_t st) {
-  return conv5_mi(d) == C5_MI_S ? abl5_split_mi<SK, C5_MI_S>(d, abl, st) : abl5_split_mi<SK, C5_MI>(d, abl, st);
+static int abl5_split(const unet_conv_desc* d, const Conv5Route& r, int abl, hipStream_t st) {
+  return r.mi == C5_MI_S ? abl5_split_mi<SK, C5_MI_S>(d, r.splitk, abl, st) : abl5_split_mi<SK, C5_MI>(d, r.splitk, abl, st);
 }
 
 }  // namespace unet
@@ -1249,18 +1238,20 @@ static int abl5_split(const unet_conv_desc* d, int abl, hipStream_t st) {
 // BN-activation bf16 y-mode descriptor whose map is small enough for split-K (d->workspace set); tools/conv5_ablate.py
 extern "C" int unet_diag_conv5_split_ablate(const unet_conv_desc* d, int abl, void* stream) {
   using namespace unet;
-  if (conv5_eligible(d) || d->nsrc != 1 || d->out_mode != UNET_OUT_Y || d->dtype != UNET_BF16 || d->src[0].C % 16)
-    return UNET_ERR_ARG;
+  if (d->nsrc != 1 || d->out_mode != UNET_OUT_Y || d->dtype != UNET_BF16 || d->src[0].C % 16) return UNET_ERR_ARG;
+  const Conv5Route r = conv5_route(d);
+  if (r.form != C5_SPLITK) return UNET_ERR_ARG;
   hipStream_t st = (hipStream_t)stream;
-  return d->src[0].kind == UNET_SRC_PLAIN ? abl5_split<SK5_PLAIN1>(d, abl, st) : abl5_split<SK_ACT>(d, abl, st);
+  return d->src[0].kind == UNET_SRC_PLAIN ? abl5_split<SK5_PLAIN1>(d, r, abl, st) : abl5_split<SK_ACT>(d, r, abl, st);
 }
 
 // diagnostic (not part of the C ABI header): conv5 ablations of the bf16 y-mode kernel (ABL bits above) on a
 // one-source plain or BN-activation descriptor; tools/conv5_ablate.py
 extern "C" int unet_diag_conv5_ablate(const unet_conv_desc* d, int abl, void* stream) {
   using namespace unet;
-  if (!conv5_eligible(d) || d->nsrc != 1 || d->out_mode != UNET_OUT_Y || d->dtype != UNET_BF16) return UNET_ERR_ARG;
+  if (d->nsrc != 1 || d->out_mode != UNET_OUT_Y || d->dtype != UNET_BF16 || d->src[0].C % 16) return UNET_ERR_ARG;
+  const Conv5Route r = conv5_narrow_route(d, conv5_mode());   // (past conv5w: the 64-channel kernel is the subject)
+  if (r.form != C5_PLAIN) return UNET_ERR_ARG;
   hipStream_t st = (hipStream_t)stream;
-  if (d->src[0].C % 16) return UNET_ERR_ARG;
-  return d->src[0].kind == UNET_SRC_PLAIN ? abl5<SK5_PLAIN1, 0>(d, abl, st) : abl5<SK_ACT, 0>(d, abl, st);
+  return d->src[0].kind == UNET_SRC_PLAIN ? abl5<SK5_PLAIN1, 0>(d, r.mi, abl, st) : abl5<SK_ACT, 0>(d, r.mi, abl, st);
 }

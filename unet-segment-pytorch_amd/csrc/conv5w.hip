@@ -34,6 +34,7 @@
 // more registers), accumulating fp32 gradients, ragged channel counts.
 #include "conv_mfma32.h"
 #include "lds_dma.h"
+#include "paths.h"
 
 namespace unet {
 
@@ -684,7 +685,7 @@ static int conv5w_mode() {
   return e ? (atoi(e) ? 1 : 0) : 2;
 }
 
-bool conv5w_ok(const unet_conv_desc* d) {
+bool conv5w_ok(const unet_conv_desc* d, int* mi_out) {
   const int mode = conv5w_mode();
   if (mode == 0) return false;
   // default: the BN-activation forwards with >= 256 input channels (the gated [skip, up] concats, down2.3):
@@ -726,50 +727,45 @@ bool conv5w_ok(const unet_conv_desc* d) {
   if ((double)d->N * d->H * d->W * d->Cout * 2 >= (double)OOB) return false;
   // enough 16 x 32 x 128 tiles to fill the chip, or (BN-activation y outputs only) 8 x 32 x 128 ones
   const int mi = w5_mi(d);
+  *mi_out = mi;
   return mi == 8 || (mi == 4 && d->out_mode == UNET_OUT_Y && !d->bnb_stats && s0.kind == UNET_SRC_ACT);
 }
 
-static int w5_gx(const unet_conv_desc* d) {
-  const long long mt = w5_mtiles(d, w5_mi(d));
+static int w5_gx(const unet_conv_desc* d, int mi) {
+  const long long mt = w5_mtiles(d, mi);
   long long gx = cdiv(256, d->Cout / W5_BN);   // one 8-wave workgroup per CU (LDS), persistent
   if (gx > mt) gx = mt;
   return (int)(gx < 1 ? 1 : gx);
 }
 
-int conv5w_stats_rows(const unet_conv_desc* d) { return w5_gx(d) * W5_WM; }
-
-int conv5w_variant(const unet_conv_desc* d, char* buf, int len) {
-  if (w5_mi(d) == 4) snprintf(buf, len, "conv5w_kernel<%s,4>", d->dtype == UNET_F16 ? "fp16" : "bf16");
-  else snprintf(buf, len, "conv5w_kernel<%s>", d->dtype == UNET_F16 ? "fp16" : "bf16");
-  return 0;
-}
+int conv5w_stats_rows(const unet_conv_desc* d, int mi) { return w5_gx(d, mi) * W5_WM; }
 
 template <typename T, int OM, int SK, int GATE, int MI = 8>
-static int launch5w(const unet_conv_desc* d, int prio, hipStream_t st) {
+static int launch5w(const unet_conv_desc* d, int mi, int prio, hipStream_t st) {
   if constexpr (MI == 8 && OM == W5_OM_Y && SK != W5_SK_PLAIN1) {
-    if (w5_mi(d) == 4) return launch5w<T, OM, SK, GATE, 4>(d, prio, st);
+    if (mi == 4) return launch5w<T, OM, SK, GATE, 4>(d, mi, prio, st);
   }
   const int tw = cdiv(d->W, W5_W), th = cdiv(d->H, W5_WM * MI);
   const int mt = d->N * tw * th;
-  const int gy = d->Cout / W5_BN, gx = w5_gx(d);
+  const int gy = d->Cout / W5_BN, gx = w5_gx(d, mi);
   const int nch = d->Cin / 16;
   hipLaunchKernelGGL((conv5w_kernel<T, OM, SK, GATE, MI>), dim3(gx, gy), dim3(512), 0, st, *d, tw, th, mt, nch, prio);
   return check_launch("conv5w");
 }
 
 template <typename T>
-static int dispatch5w(const unet_conv_desc* d, int prio, hipStream_t st) {
+static int dispatch5w(const unet_conv_desc* d, int mi, int prio, hipStream_t st) {
   const unet_src& s0 = d->src[0];
-  if (d->out_mode == UNET_OUT_F32) return launch5w<T, W5_OM_F32, W5_SK_PLAIN1, 0>(d, prio, st);
-  if (d->bnb_stats) return launch5w<T, W5_OM_BNB, W5_SK_PLAIN1, 0>(d, prio, st);
-  if (s0.kind == UNET_SRC_PLAIN) return launch5w<T, W5_OM_Y, W5_SK_PLAIN1, 0>(d, prio, st);
+  if (d->out_mode == UNET_OUT_F32) return launch5w<T, W5_OM_F32, W5_SK_PLAIN1, 0>(d, mi, prio, st);
+  if (d->bnb_stats) return launch5w<T, W5_OM_BNB, W5_SK_PLAIN1, 0>(d, mi, prio, st);
+  if (s0.kind == UNET_SRC_PLAIN) return launch5w<T, W5_OM_Y, W5_SK_PLAIN1, 0>(d, mi, prio, st);
   const bool g = s0.gate_p != nullptr;
-  if (d->nsrc == 1) return g ? launch5w<T, W5_OM_Y, SK_ACT, 1>(d, prio, st) : launch5w<T, W5_OM_Y, SK_ACT, 0>(d, prio, st);
-  return g ? launch5w<T, W5_OM_Y, SK_ACT_PLAIN, 1>(d, prio, st) : launch5w<T, W5_OM_Y, SK_ACT_PLAIN, 0>(d, prio, st);
+  if (d->nsrc == 1) return g ? launch5w<T, W5_OM_Y, SK_ACT, 1>(d, mi, prio, st) : launch5w<T, W5_OM_Y, SK_ACT, 0>(d, mi, prio, st);
+  return g ? launch5w<T, W5_OM_Y, SK_ACT_PLAIN, 1>(d, mi, prio, st) : launch5w<T, W5_OM_Y, SK_ACT_PLAIN, 0>(d, mi, prio, st);
 }
 
-int conv5w_run(const unet_conv_desc* d, int prio, hipStream_t st) {
-  return d->dtype == UNET_F16 ? dispatch5w<f16>(d, prio, st) : dispatch5w<bf16>(d, prio, st);
+int conv5w_run(const unet_conv_desc* d, int mi, int prio, hipStream_t st) {
+  return d->dtype == UNET_F16 ? dispatch5w<f16>(d, mi, prio, st) : dispatch5w<bf16>(d, mi, prio, st);
 }
 
 }  // namespace unet

@@ -3,6 +3,7 @@
 // 16-byte vector.  Same math and epilogues as conv2_kernel, simpler structure: the (8+2)x18 halo
 // and the chunk's weights are staged in LDS through src_gather(), one barrier pair per chunk.
 #include "conv_common.h"
+#include "paths.h"
 
 namespace unet {
 
@@ -220,7 +221,7 @@ static int launch_generic(const unet_conv_desc* d, hipStream_t st) {
 }
 
 template <typename T>
-int dispatch_generic(const unet_conv_desc* d, hipStream_t st) {
+static int dispatch_generic(const unet_conv_desc* d, hipStream_t st) {
   if (d->ksize == 3) {
     if (d->Cout <= 32) return launch_generic<T, 3, 32>(d, st);
     return launch_generic<T, 3, 64>(d, st);
@@ -229,8 +230,6 @@ int dispatch_generic(const unet_conv_desc* d, hipStream_t st) {
   return launch_generic<T, 1, 64>(d, st);
 }
 
-template int dispatch_generic<bf16>(const unet_conv_desc*, hipStream_t);
-template int dispatch_generic<f16>(const unet_conv_desc*, hipStream_t);
-template int dispatch_generic<float>(const unet_conv_desc*, hipStream_t);
+int conv_generic(const unet_conv_desc* d, hipStream_t st) { return UNET_DISPATCH_T(d->dtype, dispatch_generic<T>(d, st)); }
 
 }  // namespace unet

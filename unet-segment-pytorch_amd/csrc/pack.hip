@@ -8,6 +8,7 @@
 // The per-unit global gather it replaces read each 4-byte weight from a different cache line (47 us per
 // pack of the network's 17.6 M weights, ~1.5 TB/s effective).
 #include "conv_common.h"
+#include "paths.h"
 
 namespace unet {
 

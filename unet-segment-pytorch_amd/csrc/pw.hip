@@ -16,6 +16,7 @@
 //    ds_read_b64_tr_b16 so the pixel index runs along K; split-K partial slabs are summed in a fixed
 //    order by wgrad_reduce2 (deterministic).
 #include "conv_common.h"
+#include "paths.h"
 
 namespace unet {
 

@@ -7,6 +7,7 @@
 // gradient: per-thread 8 x (9*Cin) partial sums over a pixel range, reduced across the block, one
 // fp32 row per block; unet_colsum finishes (fixed order).
 #include "conv_src16.h"
+#include "paths.h"
 
 namespace unet {
 

@@ -7,6 +7,7 @@
 // so the [pixel][channel] tiles need no explicit transpose.  Split-K over pixel tiles into fp32 slabs,
 // reduced afterwards in a fixed order (deterministic).
 #include "conv_common.h"
+#include "paths.h"
 
 namespace unet {
 
@@ -222,17 +223,31 @@ static int launch_wgrad(const unet_wgrad_desc* d, hipStream_t st) {
   return check_launch("wgrad_reduce");
 }
 
-bool wgrad2_eligible(const unet_wgrad_desc* d, size_t* ws_bytes);  // wgrad2.hip
-int wgrad2_run(const unet_wgrad_desc* d, hipStream_t st);
-bool wgrad5_eligible(const unet_wgrad_desc* d, size_t* ws_bytes);  // wgrad5.hip
-int wgrad5_run(const unet_wgrad_desc* d, hipStream_t st);
-bool smallcin_wgrad_ok(const unet_wgrad_desc* d);  // smallcin.hip
-bool pw_wgrad_ok(const unet_wgrad_desc* d);        // pw.hip
-size_t pw_wgrad_ws(const unet_wgrad_desc* d);
-int pw_wgrad(const unet_wgrad_desc* d, hipStream_t st);
-size_t smallcin_wgrad_ws(const unet_wgrad_desc* d);
-bool smallcin_wgrad_is_mfma(const unet_wgrad_desc* d);
-int smallcin_wgrad(const unet_wgrad_desc* d, hipStream_t st);
+// the one place that chooses d's weight-gradient family, in priority order
+WgradRoute wgrad_route(const unet_wgrad_desc* d) {
+  WgradRoute r{};
+  const char* tn = dtype_name(d->dtype);
+  if (smallcin_wgrad_ok(d)) {
+    r.path = WGRAD_SMALLCIN;
+    r.workspace = smallcin_wgrad_ws(d);
+    snprintf(r.variant, sizeof(r.variant), smallcin_wgrad_is_mfma(d) ? "smallcin_wgrad_mfma_kernel<%s>" : "smallcin_wgrad_kernel<%s>", tn);
+  } else if (pw_wgrad_ok(d)) {
+    r.path = WGRAD_PW;
+    r.workspace = pw_wgrad_ws(d);
+    snprintf(r.variant, sizeof(r.variant), "pw_wgrad_kernel<%s>", tn);
+  } else if (wgrad5_eligible(d, &r.workspace)) {
+    r.path = WGRAD_WGRAD5;
+    snprintf(r.variant, sizeof(r.variant), "wgrad5_kernel<%s>", tn);
+  } else if (wgrad2_eligible(d, &r.workspace)) {
+    r.path = WGRAD_WGRAD2;
+    snprintf(r.variant, sizeof(r.variant), "wgrad2_kernel<%s,%d>", tn, d->ksize);
+  } else {
+    r.path = WGRAD_WGRAD;
+    r.workspace = wg_plan(d).ws_bytes;
+    snprintf(r.variant, sizeof(r.variant), "wgrad_kernel<%s,%d>", tn, d->ksize);
+  }
+  return r;
+}
 
 }  // namespace unet
 
@@ -240,32 +255,11 @@ using namespace unet;
 
 extern "C" {
 
-static int validate_src_w(const unet_src& s) {
-  if (s.kind < 0 || s.kind > UNET_SRC_UP_PLAIN || !s.data || s.C <= 0) return 0;
-  if ((s.kind == UNET_SRC_ACT || s.kind == UNET_SRC_POOL_ACT || s.kind == UNET_SRC_UP_ACT) && (!s.scale || !s.shift))
-    return 0;
-  if (s.gate_p && !s.gate_ab) return 0;
-  return 1;
-}
-
-size_t unet_wgrad_workspace(const unet_wgrad_desc* d) {
-  size_t b = 0;
-  if (unet::smallcin_wgrad_ok(d)) return unet::smallcin_wgrad_ws(d);
-  if (unet::pw_wgrad_ok(d)) return unet::pw_wgrad_ws(d);
-  if (unet::wgrad5_eligible(d, &b)) return b;
-  if (unet::wgrad2_eligible(d, &b)) return b;
-  return wg_plan(d).ws_bytes;
-}
+size_t unet_wgrad_workspace(const unet_wgrad_desc* d) { return wgrad_route(d).workspace; }
 
 int unet_wgrad_variant(const unet_wgrad_desc* d, char* buf, int len) {
   if (!d || !buf || len <= 0) return UNET_ERR_ARG;
-  const char* tn = d->dtype == UNET_F16 ? "fp16" : d->dtype == UNET_BF16 ? "bf16" : "fp32";
-  if (unet::smallcin_wgrad_ok(d))
-    snprintf(buf, len, unet::smallcin_wgrad_is_mfma(d) ? "smallcin_wgrad_mfma_kernel<%s>" : "smallcin_wgrad_kernel<%s>", tn);
-  else if (unet::pw_wgrad_ok(d)) snprintf(buf, len, "pw_wgrad_kernel<%s>", tn);
-  else if (unet::wgrad5_eligible(d, nullptr)) snprintf(buf, len, "wgrad5_kernel<%s>", tn);
-  else if (unet::wgrad2_eligible(d, nullptr)) snprintf(buf, len, "wgrad2_kernel<%s,%d>", tn, d->ksize);
-  else snprintf(buf, len, "wgrad_kernel<%s,%d>", tn, d->ksize);
+  snprintf(buf, len, "%s", wgrad_route(d).variant);
   return 0;
 }
 
@@ -277,15 +271,18 @@ int unet_conv_wgrad(const unet_wgrad_desc* d, void* stream) {
   }
   int csum = 0;
   for (int i = 0; i < d->nsrc; ++i) {
-    if (!validate_src_w(d->src[i])) { set_error("unet_conv_wgrad: bad source"); return UNET_ERR_ARG; }
+    if (!validate_src(d->src[i])) { set_error("unet_conv_wgrad: bad source"); return UNET_ERR_ARG; }
     csum += d->src[i].C;
   }
   if (csum != d->Cin) { set_error("unet_conv_wgrad: source channels != Cin"); return UNET_ERR_ARG; }
   hipStream_t st = (hipStream_t)stream;
-  if (unet::smallcin_wgrad_ok(d)) return unet::smallcin_wgrad(d, st);
-  if (unet::pw_wgrad_ok(d)) return unet::pw_wgrad(d, st);
-  if (unet::wgrad5_eligible(d, nullptr)) return unet::wgrad5_run(d, st);
-  if (unet::wgrad2_eligible(d, nullptr)) return unet::wgrad2_run(d, st);
+  switch (wgrad_route(d).path) {
+    case WGRAD_SMALLCIN: return smallcin_wgrad(d, st);
+    case WGRAD_PW: return pw_wgrad(d, st);
+    case WGRAD_WGRAD5: return wgrad5_run(d, st);
+    case WGRAD_WGRAD2: return wgrad2_run(d, st);
+    case WGRAD_WGRAD: break;
+  }
   if (d->dtype == UNET_BF16) return d->ksize == 3 ? launch_wgrad<bf16, 3>(d, st) : launch_wgrad<bf16, 1>(d, st);
   if (d->dtype == UNET_F16) return d->ksize == 3 ? launch_wgrad<f16, 3>(d, st) : launch_wgrad<f16, 1>(d, st);
   if (d->dtype == UNET_F32) return d->ksize == 3 ? launch_wgrad<float, 3>(d, st) : launch_wgrad<float, 1>(d, st);

@@ -14,13 +14,12 @@
 //  * partial sums go to an fp32 slab per split in OIHW order; wgrad_reduce2 sums the slabs in a fixed
 //    order (deterministic) with 16-byte accesses.
 #include "halo_items.h"
+#include "paths.h"
 
 namespace unet {
 
 constexpr int W2_TH = 8, W2_TW = 16, W2_BM = 128;
-constexpr int W2_RG = 32, W2_RG_MIN = 32;  // two-pass slab reduction above W2_RG_MIN splits
-int slab_reduce_two_pass(const float* ws, int splits, long long total, float* scratch, float* dw, int accum,
-                         hipStream_t st);  // pw.hip (W2_RG == PW_RG partial slabs)
+constexpr int W2_RG = 32, W2_RG_MIN = 32;  // two-pass slab reduction above W2_RG_MIN splits (W2_RG == pw.hip PW_RG partial slabs)
 
 template <typename T>
 __device__ __forceinline__ typename Mma<T>::frag tr8(const T* r0, const T* r1) {

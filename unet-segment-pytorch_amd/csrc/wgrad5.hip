@@ -26,13 +26,11 @@
 // WK = 2 the two halves' accumulators are summed through LDS before the slab store.
 #include "conv_src16.h"
 #include "lds_dma.h"
+#include "paths.h"
 
 namespace unet {
 
 constexpr int W5_TW = 32, W5_HW = 34, W5_NW = 8, W5_NT = 512;
-int slab_reduce_two_pass(const float* ws, int splits, long long total, float* scratch, float* dw, int accum,
-                         hipStream_t st);                                                   // pw.hip
-int wgrad_reduce2_launch(const float* ws, int splits, long long total, float* dw, int accum, hipStream_t st);  // wgrad2.hip
 constexpr int W5_RG = 32, W5_RG_MIN = 32;   // as wgrad2: slab reduction scratch above 32 splits
 constexpr int W5_ACT_NG = 4;   // SK value of wgrad5 only: BN-activation source without the attention gate
 

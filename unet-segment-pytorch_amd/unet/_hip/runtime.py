@@ -96,7 +96,7 @@ probe = KernelProbe()
 
 
 def conv_kernel_name(d) -> str:
-    """Instantiation unet_conv dispatches this descriptor to (csrc/conv.hip dispatch_conv)."""
+    """Instantiation unet_conv dispatches this descriptor to (csrc/conv.hip conv_route)."""
     buf = ctypes.create_string_buffer(128)
     L.load().unet_conv_variant(d, buf, 128)
     return buf.value.decode()
