@@ -1,12 +1,13 @@
-"""fp64 references of the streaming kernels around the convolutions (csrc/bn.hip, csrc/gate.hip and the
-OutConv part of csrc/misc.hip), written from the maths of nn.BatchNorm2d, ReLU and AttentionGate
-(layers.py:126-192), not from the kernels.  Pure torch; every function takes the kernels' own operands (any
-dtype, any device), evaluates in float64 and returns what the matching entry point must produce, plus the
-sums of absolute terms ("natural scales") that the tests gate the fp32 sums against.
+"""fp64 references of the streaming kernels around the convolutions (csrc/bn.hip, csrc/gate.hip, csrc/loss.hip and
+csrc/misc.hip: OutConv, resampling, the ConvTranspose2d backward prep, max-pool, materialised sources, layouts),
+written from the maths of nn.BatchNorm2d, ReLU, AttentionGate (layers.py:126-192), the Dice / balanced
+cross-entropy losses (loss.py:18-229), bilinear interpolation and MaxPool2d, not from the kernels.  Pure torch; every
+function takes the kernels' own operands (any dtype, any device), evaluates in float64 and returns what the matching
+entry point must produce, plus the sums of absolute terms ("natural scales") that the tests gate the fp32 sums against.
 
-Layouts: activations [P, C] (NHWC flattened over pixels), per-channel vectors [C], affine pairs [2, C]
-(scale, shift), coefficient triples [3, C] (A, B, Cc), OutConv logits [N, K, H, W].
-tests/test_ref_ops_cpu.py proves the formulas against torch autograd."""
+Layouts: activations [P, C] (NHWC flattened over pixels) or [N, H, W, C], per-channel vectors [C], affine pairs
+[2, C] (scale, shift), coefficient triples [3, C] (A, B, Cc), OutConv logits [N, K, H, W], loss logits [N, K, HW].
+tests/test_ref_ops_cpu.py proves the formulas against torch autograd, nn.functional and the oracle's losses."""
 
 from types import SimpleNamespace as NS
 
@@ -212,6 +213,278 @@ def outconv_bn_apply(y, scale, shift, relu, w, dl, coef):
     r.narrow_terms = r.abs_terms
     r.abs_terms = r.abs_terms + d(coef)[0].abs() * (ag - g.abs())
     return r
+
+
+# ---- DiceBCE / Dice / BalancedCE loss (csrc/loss.hip) -----------------------------------------------
+# Fields of one image, [4 + 3K]: n0 = #[t=0], n1 = #[t=1], S0 = Σ_{t=0} ce, S1 = Σ_{t=1} ce, then per class
+# (I_c = Σ p_c·[t=c], P_c = Σ p_c, T_c = #[t=c]).  A label outside [0, K) is a pixel with an all-zero one-hot row
+# and cross-entropy weight 0; its softmax still counts in P_c.  Every term is >= 0, so a field is its own
+# natural scale.
+
+def loss_cfg(ce_w=1.0, dice_w=1.0, class_w=0.5, ce_smooth=1e-6, dice_smooth=1.0, ignore_bg=1, reduction=0):
+    """reduction: 0 mean, 1 sum, 2 none (the Dice term per (n, c); the cross-entropy term is always a mean)"""
+    return NS(ce_w=ce_w, dice_w=dice_w, class_w=class_w, ce_smooth=ce_smooth, dice_smooth=dice_smooth,
+              ignore_bg=int(ignore_bg), reduction=int(reduction))
+
+
+def loss_pixel_fields(z, t, dtype=torch.float64):
+    """z [N, K, HW] logits, t [N, HW] integer labels -> the per-pixel terms of the fields [N, 4 + 3K, HW]
+    (differentiable in z) and their absolute terms: the fields' own, except S0 / S1, whose ce = lse − z_t is a
+    difference (|lse| + |z_t|).  dtype float32: the same in plain fp32 torch, for measuring what fp32 costs."""
+    z = z.to(dtype)
+    N, K, HW = z.shape
+    valid = (t >= 0) & (t < K)
+    tc = t.clamp(0, K - 1)
+    oh = F.one_hot(tc, K).permute(0, 2, 1).to(dtype) * valid.unsqueeze(1).to(dtype)
+    p = torch.softmax(z, 1)
+    lse, zt = torch.logsumexp(z, 1), z.gather(1, tc.unsqueeze(1)).squeeze(1)
+    ce, ace = (lse - zt) * valid.to(dtype), (lse.abs() + zt.abs()) * valid.to(dtype)
+    m0, m1 = (t == 0).to(dtype), (t == 1).to(dtype) * float(K > 1)
+    per_class = torch.stack([p * oh, p, oh], 2).reshape(N, 3 * K, HW)
+    px = torch.cat([torch.stack([m0, m1, ce * m0, ce * m1], 1), per_class], 1)
+    return px, torch.cat([torch.stack([m0, m1, ace * m0, ace * m1], 1), per_class], 1).detach()
+
+
+def loss_fields(z, t, dtype=torch.float64):
+    """fields [N, 4 + 3K]"""
+    return loss_pixel_fields(z, t, dtype)[0].sum(-1)
+
+
+def loss_partial(z, t, rows, dtype=torch.float64):
+    """the partial table [N, rows, 4 + 3K] and its absolute terms: row r holds the fields of the pixels
+    [r·per, (r+1)·per), per = ceil(HW / rows)"""
+    HW = z.shape[-1]
+    per = (HW + rows - 1) // rows
+    out = []
+    for px in loss_pixel_fields(z, t, dtype):
+        px = F.pad(px, [0, rows * per - HW])
+        out.append(px.reshape(px.shape[0], px.shape[1], rows, per).sum(-1).permute(0, 2, 1))
+    return NS(part=out[0], abs_terms=out[1])
+
+
+def _loss_split(fields, K):
+    f = fields
+    pc = f[:, 4:].reshape(f.shape[0], K, 3)
+    return f[:, 0], f[:, 1], f[:, 2], f[:, 3], pc[..., 0], pc[..., 1], pc[..., 2]
+
+
+def loss_value(fields, K, cfg):
+    """the loss from the per-image fields: ce_w·mean_n((1−cw)·S0/(n0+cs) + cw·S1/(n1+cs)) + dice_w·dice, with
+    D_nc = (2I + ds)/(P + T + ds) over the classes c >= c_lo: mean 1 − mean(D), sum Σ(1 − D); none: the
+    [N, K − c_lo] table 1 − D alone (DiceLoss(reduction='none'); no scalar to add a cross-entropy to).
+    Also the largest term (abs), for a gate where the terms cancel."""
+    n0, n1, S0, S1, I, P, T = _loss_split(fields, K)
+    c_lo = 1 if (cfg.ignore_bg and K > 1) else 0
+    D = ((2 * I + cfg.dice_smooth) / (P + T + cfg.dice_smooth))[:, c_lo:]
+    if cfg.reduction == 2:
+        return NS(loss=1 - D, abs=1 + D.abs())
+    ce = ((1 - cfg.class_w) * S0 / (n0 + cfg.ce_smooth) + cfg.class_w * S1 / (n1 + cfg.ce_smooth)).mean()
+    dl = 1 - D.mean() if cfg.reduction == 0 else (1 - D).sum()
+    return NS(loss=cfg.ce_w * ce + cfg.dice_w * dl,
+              abs=abs(cfg.ce_w) * ce.abs() + abs(cfg.dice_w) * (1 + D.abs().mean() if cfg.reduction == 0 else D.numel() + D.abs().sum()))
+
+
+def loss_coef(fields, K, cfg, set_w=1.0):
+    """the coefficient table [N, 2 + 2K] = (w0, w1, gA[K], gB[K]) of
+    dz_k = w_t·(p_k − [k=t]) + G_k·p_k − p_k·Σ_c G_c·p_c,  G_c = gA_c·[t=c] + gB_c:
+    w_i = set_w·ce_w·cw_i/(n_i + cs)/N; with U = P + T + ds and r = dice_w·set_w·(1/(N·nd) for mean, else 1):
+    gA = −2r/U, gB = r·(2I + ds)/U² (∂(1−D)/∂p at a pixel = −2[t=c]/U + (2I+ds)/U²); 0 for c < c_lo"""
+    n0, n1, S0, S1, I, P, T = _loss_split(d(fields), K)
+    N = fields.shape[0]
+    c_lo = 1 if (cfg.ignore_bg and K > 1) else 0
+    r = cfg.dice_w * set_w * (1.0 / (N * (K - c_lo)) if cfg.reduction == 0 else 1.0)
+    U = P + T + cfg.dice_smooth
+    gA, gB = -2 * r / U, r * (2 * I + cfg.dice_smooth) / (U * U)
+    gA[:, :c_lo] = 0
+    gB[:, :c_lo] = 0
+    w0 = set_w * cfg.ce_w * (1 - cfg.class_w) / (n0 + cfg.ce_smooth) / N
+    w1 = set_w * cfg.ce_w * cfg.class_w / (n1 + cfg.ce_smooth) / N
+    return torch.cat([w0.unsqueeze(-1), w1.unsqueeze(-1), gA, gB], -1)
+
+
+def loss_dz(z, t, cfg, gout, set_w=1.0, dtype=torch.float64):
+    """dz = gout · ∂loss/∂z by torch autograd through loss_fields and loss_value.  gout: a scalar, or [N, K − c_lo]
+    for reduction none, where it multiplies the Dice table (the cross-entropy term, a scalar, keeps factor 1)"""
+    K = z.shape[1]
+    zz = z.detach().to(dtype).clone().requires_grad_(True)
+    f = loss_fields(zz, t, dtype)
+    go = torch.as_tensor(gout, dtype=dtype, device=z.device)
+    if cfg.reduction == 2:
+        mean = loss_cfg(cfg.ce_w, 0.0, cfg.class_w, cfg.ce_smooth, cfg.dice_smooth, cfg.ignore_bg, 0)
+        total = cfg.dice_w * (loss_value(f, K, cfg).loss * go).sum() + loss_value(f, K, mean).loss
+    else:
+        total = loss_value(f, K, cfg).loss * go
+    (set_w * total).backward()
+    return zz.grad
+
+
+def loss_dz_terms(z, t, coef, gout, per_elem, ignore_bg):
+    """dz from a coefficient table by the formula of loss_coef, and the sum of its absolute terms"""
+    z, coef = d(z), d(coef)
+    N, K, HW = z.shape
+    c_lo = 1 if (ignore_bg and K > 1) else 0
+    valid = (t >= 0) & (t < K)
+    oh = F.one_hot(t.clamp(0, K - 1), K).permute(0, 2, 1).double() * valid.unsqueeze(1)
+    p = torch.softmax(z, 1)
+    wt = coef[:, 0:1] * (t == 0) + coef[:, 1:2] * ((t == 1) & (K > 1))                # [N, HW]
+    G = coef[:, 2:2 + K].unsqueeze(-1) * oh + coef[:, 2 + K:].unsqueeze(-1)         # [N, K, HW]
+    go = torch.as_tensor(gout, dtype=torch.float64, device=z.device)
+    if per_elem:
+        G[:, c_lo:] = G[:, c_lo:] * go.reshape(N, K - c_lo, 1)
+        go = torch.ones((), dtype=torch.float64, device=z.device)
+    sgp, asgp = (G * p).sum(1, keepdim=True), (G * p).abs().sum(1, keepdim=True)
+    dz = go * (wt.unsqueeze(1) * (p - oh) + G * p - p * sgp)
+    terms = go.abs() * (wt.abs().unsqueeze(1) * (p + oh) + (G * p).abs() + p * asgp)
+    return NS(dz=dz, abs_terms=terms)
+
+
+# ---- bilinear resampling, align_corners=True (csrc/misc.hip) ----------------------------------------
+
+def resize(x, Ho, Wo):
+    """x [..., Hi, Wi] (NCHW) -> [..., Ho, Wo]"""
+    return F.interpolate(d(x), size=(Ho, Wo), mode="bilinear", align_corners=True)
+
+
+def resize_bwd(dy, Hi, Wi, dx_old=None):
+    """the adjoint of resize at dy [NC..., Ho, Wo], by autograd"""
+    dy = d(dy)
+    x = torch.zeros(*dy.shape[:-2], Hi, Wi, dtype=torch.float64, device=dy.device, requires_grad=True)
+    resize(x, dy.shape[-2], dy.shape[-1]).backward(dy)
+    return x.grad if dx_old is None else x.grad + d(dx_old)
+
+
+def lin_axis(n_in, n_out, device="cpu"):
+    """the taps of one axis: i0, i1, λ per destination index, the dense weight matrix [n_out, n_in] and its support"""
+    o = torch.arange(n_out, dtype=torch.float64, device=device)
+    s = o * ((n_in - 1) / (n_out - 1) if n_out > 1 else 0.0)
+    i0 = s.floor().clamp(0, n_in - 1).long()
+    i1 = (i0 + 1).clamp(max=n_in - 1)
+    lam = (s - i0).clamp(0, 1)
+    Wm = torch.zeros(n_out, n_in, dtype=torch.float64, device=device)
+    r = torch.arange(n_out, device=device)
+    Wm[r, i0] += 1 - lam
+    Wm[r, i1] += lam
+    Sm = torch.zeros_like(Wm)
+    Sm[r, i0] = 1
+    Sm[r, i1] = 1
+    return NS(i0=i0, i1=i1, lam=lam, W=Wm, S=Sm)
+
+
+def resize_terms(x, Ho, Wo):
+    """Σ_taps w·|x| and max_taps |x| per destination element (the a-priori fp32 bound's operands)"""
+    a = d(x).abs()
+    ay, ax = lin_axis(x.shape[-2], Ho, x.device), lin_axis(x.shape[-1], Wo, x.device)
+    c = [a[..., iy, :][..., ix] for iy in (ay.i0, ay.i1) for ix in (ax.i0, ax.i1)]
+    return NS(sum_w=ay.W @ a @ ax.W.T, max_a=torch.stack(c).amax(0))
+
+
+def resize_bwd_terms(dy, Hi, Wi):
+    """the same summed over the destination taps of each source element: Σ w·|dy| and Σ_{taps} |dy|"""
+    a = d(dy).abs()
+    ay, ax = lin_axis(Hi, dy.shape[-2], dy.device), lin_axis(Wi, dy.shape[-1], dy.device)
+    return NS(sum_w=ay.W.T @ a @ ax.W, sum_a=ay.S.T @ a @ ax.S)
+
+
+def upsample_bwd(d_up, Hs, Ws, up_h, up_w, pad_t, pad_l, dx_old=None):
+    """d_up [N, Hp, Wp, C] (NHWC): the adjoint of F.pad(resize(x, up_h, up_w)) at the padded frame -> [N, Hs, Ws, C]"""
+    g = d(d_up).permute(0, 3, 1, 2)
+    N, C, Hp, Wp = g.shape
+    x = torch.zeros(N, C, Hs, Ws, dtype=torch.float64, device=g.device, requires_grad=True)
+    u = F.pad(resize(x, up_h, up_w), [pad_l, Wp - up_w - pad_l, pad_t, Hp - up_h - pad_t])
+    u.backward(g)
+    r = x.grad.permute(0, 2, 3, 1)
+    return r if dx_old is None else r + d(dx_old)
+
+
+# ---- ConvTranspose2d(k=2, s=2) backward prep ---------------------------------------------------------
+
+def convt_bwd_prep(d_up, h, w, pad_t, pad_l):
+    """d_up [N, Hp, Wp, Ct] -> s2d [N, h, w, 4·Ct], channel (2a+b)·Ct + c = d_up[n, pad_t+2y+a, pad_l+2x+b, c]
+    (a selection: exact), the bias gradient Σ over the placed region [Ct] and Σ|·|"""
+    N, _, _, Ct = d_up.shape
+    g = d(d_up)[:, pad_t:pad_t + 2 * h, pad_l:pad_l + 2 * w]
+    s2d = g.reshape(N, h, 2, w, 2, Ct).permute(0, 1, 3, 2, 4, 5).reshape(N, h, w, 4 * Ct)
+    return NS(s2d=s2d, bias=g.sum((0, 1, 2)), abs_bias=g.abs().sum((0, 1, 2)))
+
+
+# ---- MaxPool2d(2) of an activation, materialised sources, layouts -----------------------------------
+
+def pool_windows(a, H, W):
+    """a [N, Hs, Ws, C] (Hs >= 2H, Ws >= 2W) -> [N, H, W, 4, C], the windows in row-major order"""
+    N, _, _, C = a.shape
+    return a[:, :2 * H, :2 * W].reshape(N, H, 2, W, 2, C).permute(0, 1, 3, 2, 4, 5).reshape(N, H, W, 4, C)
+
+
+def maxpool_act(y, scale, shift, relu, H, W):
+    """max over the 2x2 windows of relu?(y·scale + shift) and the argmax code 0..3: the first maximum wins, and a
+    NaN replaces whatever came before it (ATen's `val > max || isnan(val)`)"""
+    win = pool_windows(act(y, scale, shift, relu), H, W)
+    best, code = win[..., 0, :], torch.zeros_like(win[..., 0, :], dtype=torch.uint8)
+    for q in range(1, 4):
+        v = win[..., q, :]
+        upd = (v > best) | v.isnan()
+        best, code = torch.where(upd, v, best), torch.where(upd, torch.full_like(code, q), code)
+    return NS(out=best, code=code, win=win)
+
+
+def place(u, H, W, pad_t, pad_l):
+    """F.pad of u [N, uh, uw, C] into an [N, H, W, C] frame at (pad_t, pad_l)"""
+    return F.pad(u, [0, 0, pad_l, W - u.shape[2] - pad_l, pad_t, H - u.shape[1] - pad_t])
+
+
+def materialize(kind, x, H, W, scale=None, shift=None, relu=0, gate_p=None, gate_ab=None, up=None):
+    """the six source kinds as a plain [N, H, W, C] map.  kind: 'plain', 'act' (gate_p [N, H, W], gate_ab [2]:
+    times sigmoid(p·a + b)), 'pool_act', 'up_act' and 'up_plain' (up = (up_h, up_w, pad_t, pad_l)).
+    abs_terms: the absolute terms of the affine, carried through the same map (None for plain copies)"""
+    x = d(x)
+    aff = scale is not None
+    a = act(x, scale, shift, relu) if aff else x
+    mag = (x * d(scale)).abs() + d(shift).abs() if aff else x.abs()
+    if kind == "plain":
+        return NS(out=x, abs_terms=None)
+    if kind == "act":
+        if gate_p is None:
+            return NS(out=a, abs_terms=mag, q=None)
+        ab = d(gate_ab)
+        q = d(gate_p) * ab[0] + ab[1]
+        return NS(out=a * torch.sigmoid(q).unsqueeze(-1), abs_terms=mag, q=q, act=a,
+                  abs_q=(d(gate_p) * ab[0]).abs() + ab[1].abs())
+    if kind == "pool_act":
+        return NS(out=maxpool_act(x, scale, shift, relu, H, W).out, abs_terms=pool_windows(mag, H, W).amax(3))
+    up_h, up_w, pad_t, pad_l = up
+    if kind == "up_plain":
+        return NS(out=place(x[:, :up_h, :up_w], H, W, pad_t, pad_l), abs_terms=None)
+    assert kind == "up_act"
+    u = resize(a.permute(0, 3, 1, 2), up_h, up_w).permute(0, 2, 3, 1)
+    t = resize_terms(a.permute(0, 3, 1, 2), up_h, up_w)
+    return NS(out=place(u, H, W, pad_t, pad_l), sum_w=place(t.sum_w.permute(0, 2, 3, 1), H, W, pad_t, pad_l),
+              max_a=place(t.max_a.permute(0, 2, 3, 1), H, W, pad_t, pad_l))
+
+
+def nchw_to_nhwc(x):
+    return x.permute(0, 2, 3, 1)
+
+
+def nhwc_to_nchw(x, scale=None, shift=None, relu=0):
+    """relu?(x·scale + shift) as NCHW, and |x·scale| + |shift|"""
+    r = act(x, scale, shift, relu).permute(0, 3, 1, 2)
+    mag = d(x).abs() if scale is None else (d(x) * d(scale)).abs() + d(shift).abs()
+    return NS(out=r, abs_terms=mag.permute(0, 3, 1, 2))
+
+
+def gated_to_nchw(x, scale, shift, relu, p, ab):
+    """act(x)·sigmoid(p·a + b) as NCHW; p [N, H, W]"""
+    r = materialize("act", x, x.shape[1], x.shape[2], scale, shift, relu, p, ab)
+    return NS(out=r.out.permute(0, 3, 1, 2), act=r.act.permute(0, 3, 1, 2), abs_terms=r.abs_terms.permute(0, 3, 1, 2),
+              q=r.q.unsqueeze(1), abs_q=r.abs_q.unsqueeze(1))
+
+
+def ulp(x, dtype):
+    """spacing of `dtype` at |x| (the subnormal spacing below the normal range)"""
+    fi = torch.finfo(dtype)
+    mant = {torch.bfloat16: 7, torch.float16: 10, torch.float32: 23}[dtype]
+    _, e = torch.frexp(x.abs().clamp_min(fi.tiny))
+    return torch.ldexp(torch.ones_like(x), (e - 1 - mant).to(torch.int32)).clamp_min(fi.tiny * fi.eps)
 
 
 # ---- gates of the GPU op tests ----------------------------------------------------------------------

@@ -134,3 +134,226 @@ def test_bn_finalize_matches_batchnorm2d():
     neg = torch.tensor([[[30.0]], [[89.99]]], dtype=torch.float64)
     r = RO.bn_finalize(neg, 10, torch.ones(1), torch.zeros(1))
     assert float(r.var) == 0.0 and abs(float(r.invstd) - EPS ** -0.5) < 1e-9 and r.running_mean is None
+
+
+# ---- loss -------------------------------------------------------------------------------------------
+
+def _loss_case(seed, N, K, H, W, scale=2.0):
+    g = torch.Generator().manual_seed(seed)
+    z = torch.randn(N, K, H, W, generator=g, dtype=torch.float64) * scale
+    t = torch.randint(0, K, (N, H, W), generator=g)
+    return z, t
+
+
+def test_loss_fields_value_and_dz_match_oracle():
+    """loss_fields -> loss_value against the oracle's dice_loss / balanced_ce_loss / dice_bce_loss (all three
+    reductions, ignore_background on and off, non-default weights and smoothing), and loss_coef -> loss_dz_terms and
+    loss_dz (autograd through the reference) against autograd through the oracle; K = 1, 2, 3, 5."""
+    from oracle import unet_oracle as O
+    for K in (1, 2, 3, 5):
+        z, t = _loss_case(10 + K, 3, K, 7, 9)
+        t[0] = 0                                   # an image without foreground
+        if K > 1:
+            t[1] = 1                               # and one without background
+        zf, tf = z.flatten(2), t.flatten(1)
+        f = RO.loss_fields(zf, tf)
+        for ib in (1, 0):
+            for red, name in enumerate(("mean", "sum", "none")):
+                cfg = RO.loss_cfg(0.0, 1.0, 0.5, 1e-6, 0.7, ib, red)
+                ref = O.dice_loss(z, t, 0.7, bool(ib), name)
+                _close(RO.loss_value(f, K, cfg).loss, ref, ("dice", K, ib, name))
+                nd = K - (1 if ib and K > 1 else 0)
+                go = torch.linspace(0.3, 1.9, 3 * nd, dtype=torch.float64).reshape(3, nd) if red == 2 else 0.37
+                zz = z.clone().requires_grad_(True)
+                (O.dice_loss(zz, t, 0.7, bool(ib), name) * go).sum().backward()
+                _close(RO.loss_dz(zf, tf, cfg, go).reshape(z.shape), zz.grad, ("dice dz", K, ib, name))
+                r = RO.loss_dz_terms(zf, tf, RO.loss_coef(f, K, cfg), go, red == 2, ib)
+                _close(r.dz.reshape(z.shape), zz.grad, ("dice dz by coef", K, ib, name), 1e-11)
+                assert bool((r.abs_terms >= r.dz.abs() * (1 - 1e-12)).all())
+        cfg = RO.loss_cfg(0.8, 1.3, 0.3, 1e-6, 1.0, 1, 0)
+        zz = z.clone().requires_grad_(True)
+        ref = O.dice_bce_loss(zz, t, 0.8, 1.3, 0.3)
+        ref.backward()
+        v = RO.loss_value(f, K, cfg)
+        _close(v.loss, ref.detach(), ("dice_bce", K))
+        assert float(v.abs) >= abs(float(v.loss))
+        _close(RO.loss_dz(zf, tf, cfg, 1.0).reshape(z.shape), zz.grad, ("dice_bce dz", K))
+        _close(RO.loss_dz_terms(zf, tf, RO.loss_coef(f, K, cfg), 1.0, 0, 1).dz.reshape(z.shape), zz.grad,
+               ("dice_bce dz by coef", K), 1e-11)
+        _close(RO.loss_value(f, K, RO.loss_cfg(1.0, 0.0, 0.3, 1e-3)).loss, O.balanced_ce_loss(z, t, 0.3, 1e-3),
+               ("balanced ce", K))
+
+
+def test_loss_deep_supervision_and_partial_rows():
+    """Σ_s w_s·loss_s and the per-set dz (set weight in the coefficients) against the oracle's deep_supervision_loss;
+    the partial table's rows add up to the fields, row r covering ceil(HW / rows) pixels."""
+    from oracle import unet_oracle as O
+    K, ws = 2, [1.0, 0.4, 0.2, 0.1]
+    zs = [_loss_case(30 + s, 2, K, 5, 8)[0].requires_grad_(True) for s in range(4)]
+    t = _loss_case(40, 2, K, 5, 8)[1]
+    O.deep_supervision_loss(zs, t, O.dice_bce_loss, ws).backward()
+    cfg, tf = RO.loss_cfg(), t.flatten(1)
+    total = 0.0
+    for z, w in zip(zs, ws):
+        zf = z.detach().flatten(2)
+        f = RO.loss_fields(zf, tf)
+        total = total + w * RO.loss_value(f, K, cfg).loss
+        _close(RO.loss_dz(zf, tf, cfg, 1.0, set_w=w).reshape(z.shape), z.grad, ("dz", w))
+        _close(RO.loss_dz_terms(zf, tf, RO.loss_coef(f, K, cfg, w), 1.0, 0, 1).dz.reshape(z.shape), z.grad,
+               ("dz by coef", w), 1e-11)
+        for rows in (1, 3, 40):
+            part = RO.loss_partial(zf, tf, rows).part
+            assert part.shape == (2, rows, 4 + 3 * K)
+            _close(part.sum(1), f, ("partial", rows))
+    _close(total, O.deep_supervision_loss([z.detach() for z in zs], t, O.dice_bce_loss, ws), "deep supervision")
+    part = RO.loss_partial(zf, tf, 3).part     # HW = 40, per = 14: rows of 14, 14 and 12 pixels
+    assert part[0, :, 4 + 2::3].sum(-1).tolist() == [14.0, 14.0, 12.0]
+
+
+def test_loss_out_of_range_labels():
+    """a label < 0 or >= K: an all-zero one-hot row and cross-entropy weight 0, still counted in P_c — the fields
+    equal those of the in-range pixels plus the out-of-range pixels' softmax in P_c; dz there is the Dice
+    gradient through P alone (autograd), and the coefficient formula agrees."""
+    K = 3
+    z, t = _loss_case(50, 2, K, 6, 7)
+    zf, tf = z.flatten(2), t.flatten(1).clone()
+    bad = torch.zeros_like(tf, dtype=torch.bool)
+    bad[:, ::5] = True
+    tf[bad] = torch.tensor([-1, K, 255, -7])[torch.arange(int(bad.sum())) % 4]
+    f = RO.loss_fields(zf, tf)
+    keep = [RO.loss_fields(zf[n:n + 1][..., ~bad[n]], tf[n:n + 1][..., ~bad[n]])[0] for n in range(2)]
+    extra = torch.zeros_like(f)
+    for n in range(2):
+        extra[n, 5::3] = torch.softmax(zf[n][:, bad[n]], 0).sum(-1)
+    _close(f, torch.stack(keep) + extra, "fields")
+    for ib in (0, 1):
+        cfg = RO.loss_cfg(0.8, 1.3, 0.3, 1e-6, 1.0, ib, 1)
+        dz = RO.loss_dz(zf, tf, cfg, 0.37)
+        r = RO.loss_dz_terms(zf, tf, RO.loss_coef(f, K, cfg), 0.37, 0, ib)
+        _close(r.dz, dz, ("dz", ib), 1e-11)
+        assert float(dz[0][:, bad[0]].abs().max()) > 0
+
+
+# ---- resampling -------------------------------------------------------------------------------------
+
+RESIZE_GEO = [(8, 12, 16, 24), (8, 12, 64, 96), (7, 9, 15, 17), (9, 11, 9, 11), (1, 5, 8, 10), (5, 7, 1, 1),
+              (9, 11, 4, 5)]
+
+
+def test_resize_and_adjoints_match_dense_weight_matrices():
+    """resize (F.interpolate), resize_bwd and upsample_bwd (autograd) against Wy·x·Wxᵀ and its transpose with the
+    dense tap matrices of lin_axis (an index-level formulation); the bound operands of resize_terms /
+    resize_bwd_terms dominate the values they bound."""
+    g = torch.Generator().manual_seed(3)
+    for Hi, Wi, Ho, Wo in RESIZE_GEO:
+        x = torch.randn(2, 3, Hi, Wi, generator=g, dtype=torch.float64)
+        dy = torch.randn(2, 3, Ho, Wo, generator=g, dtype=torch.float64)
+        ay, ax = RO.lin_axis(Hi, Ho), RO.lin_axis(Wi, Wo)
+        assert bool((ay.W.sum(1) - 1).abs().max() < 1e-15) and bool((ax.W.sum(1) - 1).abs().max() < 1e-15)
+        y = RO.resize(x, Ho, Wo)
+        _close(y, ay.W @ x @ ax.W.T, ("resize", Hi, Wi, Ho, Wo))
+        old = torch.randn(2, 3, Hi, Wi, generator=g, dtype=torch.float64)
+        _close(RO.resize_bwd(dy, Hi, Wi), ay.W.T @ dy @ ax.W, ("resize_bwd", Hi, Wi, Ho, Wo))
+        _close(RO.resize_bwd(dy, Hi, Wi, old), ay.W.T @ dy @ ax.W + old, ("resize_bwd accum", Hi, Wi, Ho, Wo))
+        t = RO.resize_terms(x, Ho, Wo)
+        assert bool((t.sum_w >= y.abs() - 1e-14).all()) and bool((t.max_a >= t.sum_w - 1e-14).all())
+        tb = RO.resize_bwd_terms(dy, Hi, Wi)
+        assert bool((tb.sum_w >= RO.resize_bwd(dy, Hi, Wi).abs() - 1e-13).all()) and bool((tb.sum_a >= tb.sum_w - 1e-13).all())
+        # the padded NHWC form: unequal pads on the four sides
+        pt, pl, Hp, Wp = 1, 2, Ho + 4, Wo + 3
+        d_up = torch.randn(2, Hp, Wp, 3, generator=g, dtype=torch.float64)
+        inner = d_up[:, pt:pt + Ho, pl:pl + Wo].permute(0, 3, 1, 2)
+        _close(RO.upsample_bwd(d_up, Hi, Wi, Ho, Wo, pt, pl), (ay.W.T @ inner @ ax.W).permute(0, 2, 3, 1),
+               ("upsample_bwd", Hi, Wi, Ho, Wo))
+
+
+# ---- ConvTranspose2d backward prep, max-pool, materialised sources, layouts ---------------------------
+
+def test_convt_bwd_prep_matches_pixel_unshuffle_and_autograd():
+    g = torch.Generator().manual_seed(4)
+    N, h, w, Ct, pt, pl = 2, 3, 5, 4, 1, 2
+    Hp, Wp = 2 * h + pt + 1, 2 * w + pl + 3
+    d_up = torch.randn(N, Hp, Wp, Ct, generator=g, dtype=torch.float64)
+    r = RO.convt_bwd_prep(d_up, h, w, pt, pl)
+    inner = d_up[:, pt:pt + 2 * h, pl:pl + 2 * w].permute(0, 3, 1, 2)
+    pu = F.pixel_unshuffle(inner, 2).reshape(N, Ct, 4, h, w).permute(0, 3, 4, 2, 1).reshape(N, h, w, 4 * Ct)
+    assert torch.equal(r.s2d, pu)
+    # the s2d map is the output gradient of the equivalent 1x1 conv: with it, ConvTranspose2d's input and bias
+    # gradients come out as a matrix product and a sum
+    m = torch.nn.ConvTranspose2d(6, Ct, 2, 2).double()
+    x = torch.randn(N, 6, h, w, generator=g, dtype=torch.float64, requires_grad=True)
+    m(x).backward(inner)
+    wm = m.weight.detach().permute(2, 3, 1, 0).reshape(4 * Ct, 6)           # [(2a+b)·Ct + c][cin]
+    _close((r.s2d @ wm).permute(0, 3, 1, 2), x.grad, "dx through s2d")
+    _close(r.bias, m.bias.grad, "bias")
+    assert bool((r.abs_bias >= r.bias.abs()).all())
+
+
+def test_maxpool_act_matches_max_pool2d():
+    """values and first-maximum codes against F.max_pool2d(return_indices=True) on tie-rich data (even and odd
+    source sizes, ReLU on and off); a NaN comes out with its own position's code"""
+    g = torch.Generator().manual_seed(5)
+    for Hs, Ws in ((10, 14), (11, 15)):
+        H, W, C = Hs // 2, Ws // 2, 3
+        y = torch.randint(-32, 33, (2, Hs, Ws, C), generator=g).double() / 8
+        scale = torch.tensor([0.5, -1.0, 2.0], dtype=torch.float64)
+        shift = torch.tensor([1 / 64, -3 / 64, 0.0], dtype=torch.float64)
+        for relu in (0, 1):
+            r = RO.maxpool_act(y, scale, shift, relu, H, W)
+            a = RO.act(y, scale, shift, relu).permute(0, 3, 1, 2)
+            v, idx = F.max_pool2d(a, 2, return_indices=True)
+            yy, xx = idx // Ws, idx % Ws
+            oy = torch.arange(H).view(1, 1, H, 1)
+            ox = torch.arange(W).view(1, 1, 1, W)
+            code = 2 * (yy - 2 * oy) + (xx - 2 * ox)
+            assert torch.equal(r.out, v.permute(0, 2, 3, 1))
+            assert torch.equal(r.code.long(), code.permute(0, 2, 3, 1))
+            if relu:
+                assert int(((r.win == 0).all(3) & (r.code == 0)).sum()) > 0      # whole windows tie at 0
+    y = torch.zeros(1, 2, 8, 1, dtype=torch.float64)
+    for q in range(4):
+        y[0, q >> 1, 2 * q + (q & 1), 0] = float("nan")
+    one, zero = torch.ones(1, dtype=torch.float64), torch.zeros(1, dtype=torch.float64)
+    r = RO.maxpool_act(y, one, zero, 1, 1, 4)
+    v, idx = F.max_pool2d(torch.relu(y.permute(0, 3, 1, 2)), 2, return_indices=True)
+    assert bool(r.out.isnan().all()) and bool(v.isnan().all()) and r.code.flatten().tolist() == [0, 1, 2, 3]
+    assert (2 * (idx // 8) + idx % 8 - 2 * torch.arange(4)).flatten().tolist() == [0, 1, 2, 3]
+
+
+def test_materialize_kinds_and_layouts():
+    """the six source kinds against nn.functional on NCHW tensors, and the three layout maps element by element"""
+    g = torch.Generator().manual_seed(6)
+    N, H, W, C = 2, 6, 10, 5
+    scale, shift = torch.randn(C, generator=g, dtype=torch.float64), torch.randn(C, generator=g, dtype=torch.float64)
+    x = torch.randn(N, H, W, C, generator=g, dtype=torch.float64)
+    nchw = x.permute(0, 3, 1, 2)
+    aff = nchw * scale.view(1, C, 1, 1) + shift.view(1, C, 1, 1)
+    assert torch.equal(RO.materialize("plain", x, H, W).out, x)
+    for relu in (0, 1):
+        a = F.relu(aff) if relu else aff
+        _close(RO.materialize("act", x, H, W, scale, shift, relu).out, a.permute(0, 2, 3, 1), ("act", relu))
+        p, ab = torch.randn(N, H, W, generator=g, dtype=torch.float64), torch.tensor([1.3, -0.2], dtype=torch.float64)
+        gate = torch.sigmoid(p * 1.3 - 0.2)
+        r = RO.materialize("act", x, H, W, scale, shift, relu, p, ab)
+        _close(r.out, (a * gate.unsqueeze(1)).permute(0, 2, 3, 1), ("gated", relu))
+        rg = RO.gated_to_nchw(x, scale, shift, relu, p, ab)
+        _close(rg.out, a * gate.unsqueeze(1), ("gated_to_nchw", relu))
+        _close(RO.nhwc_to_nchw(x, scale, shift, relu).out, a, ("nhwc_to_nchw", relu))
+        assert bool((RO.nhwc_to_nchw(x, scale, shift, relu).abs_terms >= a.abs() - 1e-14).all())
+        r = RO.materialize("pool_act", x, H // 2, W // 2, scale, shift, relu)
+        _close(r.out, F.max_pool2d(a, 2).permute(0, 2, 3, 1), ("pool_act", relu))
+        up = (2 * H, 2 * W, 1, 2)
+        r = RO.materialize("up_act", x, 2 * H + 3, 2 * W + 3, scale, shift, relu, up=up)
+        ref = F.pad(F.interpolate(a, scale_factor=2, mode="bilinear", align_corners=True), [2, 1, 1, 2])
+        _close(r.out, ref.permute(0, 2, 3, 1), ("up_act", relu))
+        assert bool((r.sum_w >= r.out.abs() - 1e-14).all()) and bool((r.max_a >= r.sum_w - 1e-14).all())
+    r = RO.materialize("up_plain", x, H + 3, W + 3, up=(H, W, 1, 2))
+    assert torch.equal(r.out, F.pad(nchw, [2, 1, 1, 2]).permute(0, 2, 3, 1))
+    assert torch.equal(RO.nhwc_to_nchw(x).out, nchw)
+    back = RO.nchw_to_nhwc(nchw.contiguous())
+    for n, h, w, c in ((0, 0, 0, 0), (1, 5, 9, 4), (1, 2, 7, 3)):
+        assert float(back[n, h, w, c]) == float(nchw[n, c, h, w])
+    # ulp: the spacing at 1 and just below, and the subnormal spacing
+    one = torch.tensor([1.0, 0.99, 0.0], dtype=torch.float64)
+    assert RO.ulp(one, torch.bfloat16).tolist() == [2.0 ** -7, 2.0 ** -8, 2.0 ** -133]
+    assert RO.ulp(one, torch.float16).tolist() == [2.0 ** -10, 2.0 ** -11, 2.0 ** -24]

@@ -1021,7 +1021,8 @@ __global__ void materialize_pool_kernel(const unet_src s, long long N, int H, in
       load_vec<T>((const T*)s.data + (((n * s.H + 2 * y + (q >> 1)) * (long long)s.W + 2 * x + (q & 1)) * C + cv * VEC), v);
 #pragma unroll
       for (int j = 0; j < VEC; ++j) {
-        const float a = fmaxf(__builtin_fmaf(v[j], sc[j], sf[j]), lo);
+        const float r = __builtin_fmaf(v[j], sc[j], sf[j]);
+        const float a = r != r ? r : fmaxf(r, lo);   // fmaxf drops a NaN; relu(NaN) is NaN
         if (q == 0 || a > best[j] || a != a) { best[j] = a; arg[j] = q; }
       }
     }
