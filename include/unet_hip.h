@@ -27,8 +27,9 @@ extern "C" {
 #endif
 
 /* unet_version() of a library built from this header.  110: unet_conv_desc gained `workspace` (round 5);
- * a caller built against an older header must not pass its (shorter) descriptors to this library */
-#define UNET_ABI_VERSION 110
+ * a caller built against an older header must not pass its (shorter) descriptors to this library.
+ * 111: unet_aug_params, unet_aug_elastic_field and unet_aug_apply added (no existing layout changed) */
+#define UNET_ABI_VERSION 111
 
 enum { UNET_F32 = 0, UNET_BF16 = 1, UNET_F16 = 2 };  /* operand (activation / weight) type */
 enum { UNET_ERR_ARG = 1001, UNET_ERR_UNSUPPORTED = 1002 };
@@ -382,6 +383,51 @@ int unet_slice_finish(long long N, int H, int W, const uint8_t* img, int roundtr
  * softmax(logits[n, :, ytab[y], xtab[x]])[cls] > threshold, else 0 (PIL NEAREST tables).           */
 int unet_postprocess_mask(long long N, int K, int H, int W, const float* logits, int cls, float threshold, int outH,
                           int outW, const int32_t* ytab, const int32_t* xtab, uint8_t* out, void* stream);
+
+/* ---- device training augmentation (csrc/augment.hip) ------------------------- */
+/* The device form of get_train_transforms (augmentations.py:26-89).  Every random decision is drawn on
+ * the host into one row per sample; the kernels are deterministic given the table. */
+enum {
+  UNET_AUG_HFLIP = 1,       /* x -> S-1-x of the source                                   */
+  UNET_AUG_VFLIP = 2,       /* y -> S-1-y of the source                                   */
+  UNET_AUG_AFFINE = 4,      /* s = inv_affine * r                                         */
+  UNET_AUG_ELASTIC = 8,     /* r = q + d(q), d = field[elastic_slot]                      */
+  UNET_AUG_GRID = 16,       /* q = (gx(x), gy(y)), piecewise linear, 6 knots per axis     */
+  UNET_AUG_BRIGHTNESS = 32, /* v = clip(contrast * v + brightness, 0, 1)                  */
+  UNET_AUG_NOISE = 64,      /* v = clip(v + noise_sigma * n, 0, 1), n ~ N(0,1) per pixel  */
+  UNET_AUG_DROPOUT = 128    /* v = 0 inside each of n_holes rectangles (mask untouched)   */
+};
+typedef struct unet_aug_params {
+  uint32_t flags;           /* UNET_AUG_* bits                                                          */
+  float inv_affine[6];      /* row-major 2x3: sx = a0*rx + a1*ry + a2, sy = a3*rx + a4*ry + a5          */
+  float gx[6], gy[6];       /* source knots of the grid distortion at output positions k*S/5            */
+  float contrast, brightness, noise_sigma;
+  uint32_t key[2];          /* Philox4x32-10 key of this sample                                         */
+  int32_t n_holes;          /* 0..4                                                                     */
+  int32_t holes[4][4];      /* x0, y0, x1, y1 (end exclusive), output pixels                            */
+  int32_t elastic_slot;     /* index into the compact field buffer, or -1                               */
+} unet_aug_params;
+/* Elastic displacement fields of the n_slots samples table[slots[i]] (device int32 list): field fp32
+ * [n_slots][2][S][S] (dx, dy) = alpha * (G * u), u i.i.d. uniform on [-1, 1) from Philox4x32-10 with the
+ * sample's key, counter (y*S + x, 1 + component, 0, 0), u = (w0 >> 8) * 2^-23 - 1; G the separable
+ * filter taps[2R+1] (device fp32) with the reflect-101 border.  tmp: scratch of the field's size.
+ * Requires S > R (UNET_ERR_ARG) and R <= 96 (UNET_ERR_UNSUPPORTED).                                   */
+int unet_aug_elastic_field(int n_slots, int S, float alpha, int R, const float* taps, long long N,
+                           const unet_aug_params* table, const int32_t* slots, float* tmp, float* field,
+                           void* stream);
+/* One launch: out_img fp32 (N,1,S,S) and, if mask != NULL, out_mask int64 (N,S,S) from the resized uint8
+ * images img (N,S,S), the original masks (N,mask_h,mask_w) read through PIL NEAREST tables ytab[S] /
+ * xtab[S], and the device table of table_len == N rows.  Per output pixel: one coordinate map (grid ->
+ * elastic -> inverse affine -> flips), one bilinear image fetch (/255, taps outside the frame are 0), one
+ * nearest mask fetch (> 127; 0 outside), then brightness/contrast, noise (Philox counter (y*S + x, 0, 0,
+ * 0): u1 = ((w0 >> 8) + 1) * 2^-24, u2 = (w1 >> 8) * 2^-24, n = sqrt(-2 ln u1) cos(2 pi u2)), dropout and
+ * (v - mean) / std.  A row without AFFINE / ELASTIC / GRID copies (mirrored) pixels exactly as
+ * unet_slice_finish does.  field: the buffer of unet_aug_elastic_field with n_elastic slots (may be NULL
+ * when n_elastic == 0; a row whose slot is outside [0, n_elastic) gets no displacement).              */
+int unet_aug_apply(long long N, int S, const uint8_t* img, int mask_h, int mask_w, const uint8_t* mask,
+                   const int32_t* ytab, const int32_t* xtab, const unet_aug_params* table, long long table_len,
+                   const float* field, int n_elastic, float mean, float stdv, float* out_img, int64_t* out_mask,
+                   void* stream);
 
 #ifdef __cplusplus
 }

@@ -64,6 +64,15 @@ class WgradDesc(ctypes.Structure):
                 ("workspace", c_vp)]
 
 
+class AugParams(ctypes.Structure):     # unet_aug_params (42 x 4 bytes; AUG_DTYPE in utils/gpu_pipeline.py mirrors it)
+    _fields_ = [("flags", ctypes.c_uint32), ("inv_affine", c_float * 6), ("gx", c_float * 6), ("gy", c_float * 6),
+                ("contrast", c_float), ("brightness", c_float), ("noise_sigma", c_float), ("key", ctypes.c_uint32 * 2),
+                ("n_holes", ctypes.c_int32), ("holes", (ctypes.c_int32 * 4) * 4), ("elastic_slot", ctypes.c_int32)]
+
+
+AUG_HFLIP, AUG_VFLIP, AUG_AFFINE, AUG_ELASTIC, AUG_GRID, AUG_BRIGHTNESS, AUG_NOISE, AUG_DROPOUT = (
+    1, 2, 4, 8, 16, 32, 64, 128)
+
 # name -> (restype, argtypes); mirrors include/unet_hip.h
 _SIGS = {
     "unet_last_error": (ctypes.c_char_p, []),
@@ -145,10 +154,13 @@ _SIGS = {
                                          c_float, c_float, c_float, c_int, c_int, c_vp, c_vp, c_vp]),
     "unet_loss_grad_multi": (c_int, [c_int, c_ll, c_int, c_ll, ctypes.POINTER(c_vp), c_vp, c_vp, c_vp, c_int, c_int,
                                      ctypes.POINTER(c_vp), c_vp]),
+    "unet_aug_elastic_field": (c_int, [c_int, c_int, c_float, c_int, c_vp, c_ll, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "unet_aug_apply": (c_int, [c_ll, c_int, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_ll, c_vp, c_int, c_float,
+                               c_float, c_vp, c_vp, c_vp]),
 }
 
 _lib = None
-ABI_VERSION = 110   # include/unet_hip.h UNET_ABI_VERSION
+ABI_VERSION = 111   # include/unet_hip.h UNET_ABI_VERSION
 
 # UNET_GUARD=1: bounds-checking debug mode (csrc/guard_alloc.cpp).  Every device allocation of the process
 # gets guard bands and every library call is bracketed by a device sync + a check of all bands, so an

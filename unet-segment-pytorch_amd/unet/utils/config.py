@@ -6,7 +6,9 @@ Keys read (reference meaning unchanged):
   model.type (unet | attention_unet | attention), model.n_channels, model.n_classes, model.bilinear,
   model.base_features, model.deep_supervision;
   loss.type, loss.ce_weight, loss.dice_weight, loss.class_weights, loss.balanced_class_weight,
-  loss.ds_weights (deep supervision only).
+  loss.ds_weights (deep supervision only);
+  data.img_size and augmentation.enabled / horizontal_flip / rotation_limit / elastic / brightness_contrast
+  (create_train_transform: the device form of the reference's training augmentation).
 Keys added:
   model.backend   — "hip" (the only backend of this package; anything else is an error, not a silent
                     fallback to another implementation);
@@ -67,6 +69,20 @@ def create_criterion(config: Dict[str, Any]) -> nn.Module:
     if config.get("model", {}).get("deep_supervision", False):
         return DeepSupervisionLoss(base, weights=lc.get("ds_weights", [1.0, 0.4, 0.2, 0.1]))
     return base
+
+
+def create_train_transform(config: Dict[str, Any], mean: float = 0.5, std: float = 0.5, device="cuda"):
+    """scripts/train.py:242-250: the training augmentation from `data.img_size` and the `augmentation:` section
+    (`horizontal_flip`, `elastic` and `brightness_contrast` are probabilities, `rotation_limit` degrees; the
+    defaults are train.py's), as a GpuTrainAugment.  Returns None when `augmentation.enabled` is false: the
+    caller then prepares training slices as validation ones (GpuSliceTransform without flips)."""
+    from unet.utils.gpu_pipeline import GpuTrainAugment
+    ac = config.get("augmentation") or {}
+    if not ac.get("enabled", True):
+        return None
+    return GpuTrainAugment(img_size=_section(config, "data")["img_size"], mean=mean, std=std, device=device,
+                           p_flip=ac.get("horizontal_flip", 0.5), rotation_limit=ac.get("rotation_limit", 15),
+                           p_elastic=ac.get("elastic", 0.3), p_brightness=ac.get("brightness_contrast", 0.3))
 
 
 def build_from_config(config: Union[str, Dict[str, Any]]) -> Tuple[nn.Module, nn.Module]:
