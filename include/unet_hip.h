@@ -29,7 +29,7 @@ extern "C" {
 /* unet_version() of a library built from this header.  110: unet_conv_desc gained `workspace` (round 5);
  * a caller built against an older header must not pass its (shorter) descriptors to this library.
  * 111: unet_aug_params, unet_aug_elastic_field and unet_aug_apply added (no existing layout changed) */
-#define UNET_ABI_VERSION 111
+#define UNET_ABI_VERSION 112
 
 enum { UNET_F32 = 0, UNET_BF16 = 1, UNET_F16 = 2 };  /* operand (activation / weight) type */
 enum { UNET_ERR_ARG = 1001, UNET_ERR_UNSUPPORTED = 1002 };
@@ -269,6 +269,18 @@ int unet_gate_bwd3(int dtype, long long P, int Ci, const void* gw, const void* x
 int unet_upsample_bwd(long long N, int C, int Hs, int Ws, int up_h, int up_w, int pad_t, int pad_l,
                       int Hp, int Wp, float sh, float sw, const float* d_up, float* dx, int accum,
                       void* stream);
+/* the same adjoint of d_up + W_g^T . dgw: the attention gate's W_g input gradient (1x1, Ci -> C
+ * channels; dgw op dtype NHWC [N,Hp,Wp,Ci], wt_packed = unet_pack_weight(W_g, transpose=1)) is
+ * formed as d_up is loaded instead of by an accumulating UNET_OUT_F32 unet_conv into d_up first.
+ * d_up is not written.  dx has the bits of those two calls where the conv runs on the 1x1 MFMA
+ * kernel (unet_conv_variant "pw_conv_kernel...").  _ok: whether the geometry is served (16-bit
+ * dtype, C % 64 == 0, Ci in {32, 64, 128, 256}, the tiled adjoint's window limits); the call
+ * fails otherwise                                                                                */
+int unet_upsample_bwd_pw_ok(int dtype, long long N, int C, int Hs, int Ws, int up_h, int up_w, int pad_t,
+                            int pad_l, int Hp, int Wp, float sh, float sw, int Ci);
+int unet_upsample_bwd_pw(int dtype, long long N, int C, int Hs, int Ws, int up_h, int up_w, int pad_t,
+                         int pad_l, int Hp, int Wp, float sh, float sw, const float* d_up, const void* dgw,
+                         int Ci, const void* wt_packed, float* dx, int accum, void* stream);
 /* generic fp32 NCHW bilinear resize (deep-supervision heads) fwd and bwd                         */
 int unet_resize_nchw(long long NC, int Hi, int Wi, int Ho, int Wo, float sh, float sw, const float* x,
                      float* y, void* stream);

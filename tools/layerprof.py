@@ -44,6 +44,12 @@ def _call(name, *args):
         return _orig(name, *args)
     info, fl = (_desc_info(name, args[0]) if name in ("unet_conv", "unet_conv_wgrad") else (name, 0.0))
     hb = _hbm_bytes(name, args)
+    if name == "unet_upsample_bwd_pw":
+        # the adjoint fused with the W_g dgrad (not in the bench line's hbm block): d_up and dgw read once, dx
+        # written (read too when it accumulates)
+        _, N, C, Hs, Ws, _, _, _, _, Hp, Wp = args[:11]
+        Ci, accum = args[15], args[18]
+        hb = (name, N * Hp * Wp * (4 * C + 2 * Ci) + N * Hs * Ws * C * 4 * (1 + accum))
     if hb is not None and name not in ("unet_conv", "unet_conv_wgrad"):
         info = f"{name} {hb[1] / 1e6:.1f} MB"
         fl = -hb[1]          # negative: algorithmic bytes (HBM-bound line)

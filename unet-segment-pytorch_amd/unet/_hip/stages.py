@@ -409,9 +409,12 @@ class GateStage:
     def gated_src(self) -> L.Src:
         return self.x.src_gated(self.p, self.psi_ab)
 
-    def backward(self, prec, d_xs: torch.Tensor, grads: Grads, d_gup: torch.Tensor, d_gup_accum: int):
+    def backward(self, prec, d_xs: torch.Tensor, grads: Grads, d_gup: Optional[torch.Tensor], d_gup_accum: int,
+                 defer_g: bool = False):
         """d_xs: fp32 NHWC grad of x*s.  Adds into x.grad; writes/adds W_g's input-grad into d_gup
-        (fp32 NHWC at x's size, the upsampled-g space)."""
+        (fp32 NHWC at x's size, the upsampled-g space).  defer_g: W_g's input gradient is not launched;
+        returns (dgw, W_g's packed transposed weight) for the caller's unet_upsample_bwd_pw, which forms it
+        while it reduces d_gup to g's resolution."""
         x = self.x
         dev = x.data.device
         P, Cx, Ci = x.pixels, x.C, self.ci
@@ -459,8 +462,15 @@ class GateStage:
                vp(self.xw.ab), vp(self.wpsi), vp(dq), vp(self.p), vp(pcoef), vp(gcoef), vp(xcoef), vp(dgw), vp(dxw),
                stream())
         # (4) the two 1x1 projections
-        self.cg.conv_backward(prec, dgw, self.gw_src, grads,
-                              {"mode": "f32", "out": d_gup, "accum": d_gup_accum})
+        wt_g = None
+        if defer_g:
+            wt_g = self.cg.pre_wt if self.cg.pre_wt is not None else pack_weight(self.cg.conv.weight, prec,
+                                                                                 transpose=True)
+            self.cg.pre_wt = None
+            self.cg.conv_backward(prec, dgw, self.gw_src, grads, None)
+        else:
+            self.cg.conv_backward(prec, dgw, self.gw_src, grads,
+                                  {"mode": "f32", "out": d_gup, "accum": d_gup_accum})
         dx2, acc2 = x.grad_target()
         if fuse:
             self.cx.conv_backward(prec, dxw, [x.src()], grads, {"mode": "f32_gated", "out": dx2, "accum": acc2,
@@ -468,6 +478,33 @@ class GateStage:
                                                                 "gate_ab": self.psi_ab})
         else:
             self.cx.conv_backward(prec, dxw, [x.src()], grads, {"mode": "f32", "out": dx2, "accum": acc2})
+        return (dgw, wt_g) if defer_g else None
+
+    def up_fused_ok(self, prec, g: Act, x: Act) -> bool:
+        """Whether W_g's input gradient (Ci -> g.C 1x1 at x's size, accumulated into the gradient of the x2
+        bilinear map of g) can be formed inside the bilinear adjoint (unet_upsample_bwd_pw): the result is
+        defined as that of the 1x1 MFMA kernel followed by the tiled adjoint, so both must be what the
+        two-launch path would run."""
+        if prec.code not in (L.BF16, L.F16) or os.environ.get("UNET_NO_GUP_FUSE"):   # (env: A/B switch)
+            return False
+        # per-level policy, measured at the bench size (bs 4, bf16; W_g dgrad + adjoint -> fused, us per step,
+        # profiles/r07_layerprof_gup_{off,on,deep}.txt):
+        #   Ci 32 (512^2) 173.7 -> 139.9    Ci 64 (256^2) 116.1 -> 99.5    Ci 128 (128^2) 65.2 -> 100.5    Ci 256 (64^2) 40.2 -> 86.7
+        # with 4 or 8 chunks of projection channels every wave of every 64-channel tile streams the window's dgw
+        # again (from L2) and the deep maps lose: the kernel serves them (unet_upsample_bwd_pw_ok) but they keep the
+        # two launches.  UNET_GUP_DEEP=1 fuses them too (to re-measure)
+        if self.ci > 64 and not os.environ.get("UNET_GUP_DEEP"):
+            return False
+        d = L.ConvDesc()
+        d.dtype, d.N, d.H, d.W, d.Cin, d.Cout, d.ksize, d.nsrc = prec.code, x.N, x.H, x.W, self.ci, g.C, 1, 1
+        s = L.Src()
+        s.kind, s.C, s.H, s.W = L.SRC_PLAIN, self.ci, x.H, x.W
+        d.src[0] = s
+        d.out_mode, d.split, d.accum = L.OUT_F32, g.C, 1
+        if not conv_kernel_name(d).startswith("pw_conv_kernel"):
+            return False
+        return bool(L.load().unet_upsample_bwd_pw_ok(prec.code, g.N, g.C, g.H, g.W, x.H, x.W, 0, 0, x.H, x.W,
+                                                     up_scale(g.H, x.H), up_scale(g.W, x.W), self.ci))
 
     def _wx_gated_ok(self, prec, x: Act) -> bool:
         """Whether the W_x dgrad (Ci -> Cx 1x1) runs on the kernel that serves UNET_OUT_F32_GATED."""
@@ -629,6 +666,14 @@ class UpStage:
             self.dc.backward(prec, grads, {"mode": "f32", "out": d_xs, "accum": 0, "out2": d_up, "accum2": 0,
                                            "split": x2.C})
             same = (self.convt is None and up_h == x2.H and up_w == x2.W and pt == 0 and pl == 0)
+            if same and self.gate.up_fused_ok(prec, x1, x2):
+                # d_up + W_g^T dgw is formed as the adjoint loads d_up: no read-modify-write pass over d_up
+                dgw, wt_g = self.gate.backward(prec, d_xs, grads, None, 0, defer_g=True)
+                gx, acc = x1.grad_target()
+                L.call("unet_upsample_bwd_pw", prec.code, x1.N, x1.C, x1.H, x1.W, up_h, up_w, 0, 0, x2.H, x2.W,
+                       up_scale(x1.H, up_h), up_scale(x1.W, up_w), vp(d_up), vp(dgw), self.gate.ci, vp(wt_g),
+                       vp(gx), acc, stream())
+                return
             if same:
                 self.gate.backward(prec, d_xs, grads, d_up, 1)
             else:
