@@ -524,3 +524,168 @@ def check_elem(got, ref, abs_terms, prec, what, rel32=1e-5):
     else:
         tol = rel32 * abs_terms
     assert (err <= tol).all(), (what,) + _worst(err, tol)
+
+
+# ---- convolutions (csrc/conv*.hip, pw.hip, smallcin.hip, wgrad*.hip) ---------------------------------
+# Written from the sums, as k·k shifted matrix products in the operands' own precision (fp64 in the tests), with
+# zero 'same' padding and no bias.  Each returns the result and abs_terms, the same sum over |operands|.
+
+def _shifted(x, dh, dw):
+    """z[n, h, w] = x[n, h + dh, w + dw], zero outside the map; x [N, H, W, C]"""
+    H, W = x.shape[1], x.shape[2]
+    z = torch.zeros_like(x)
+    h0, h1, w0, w1 = max(0, -dh), min(H, H - dh), max(0, -dw), min(W, W - dw)
+    if h0 < h1 and w0 < w1:
+        z[:, h0:h1, w0:w1] = x[:, h0 + dh:h1 + dh, w0 + dw:w1 + dw]
+    return z
+
+
+def conv_fwd(x, w, k):
+    """y[n,h,w,co] = Σ_{kh,kw,ci} x[n, h+kh−p, w+kw−p, ci]·w[co,ci,kh,kw], p = k // 2.  x [N,H,W,Cin] as the conv
+    reads it, w OIHW"""
+    p = k // 2
+    y = torch.zeros(*x.shape[:3], w.shape[0], dtype=x.dtype, device=x.device)
+    a = torch.zeros_like(y)
+    for kh in range(k):
+        for kw in range(k):
+            xs, wt = _shifted(x, kh - p, kw - p), w[:, :, kh, kw].T
+            y += xs @ wt
+            a += xs.abs() @ wt.abs()
+    return NS(y=y, abs_terms=a)
+
+
+def conv_dgrad(dy, w, k):
+    """dx[n,h,w,ci] = Σ_{kh,kw,co} dy[n, h+p−kh, w+p−kw, co]·w[co,ci,kh,kw]"""
+    p = k // 2
+    dx = torch.zeros(*dy.shape[:3], w.shape[1], dtype=dy.dtype, device=dy.device)
+    a = torch.zeros_like(dx)
+    for kh in range(k):
+        for kw in range(k):
+            ds, wt = _shifted(dy, p - kh, p - kw), w[:, :, kh, kw]
+            dx += ds @ wt
+            a += ds.abs() @ wt.abs()
+    return NS(dx=dx, abs_terms=a)
+
+
+def conv_wgrad(x, dy, k):
+    """dw[co,ci,kh,kw] = Σ_{n,h,w} dy[n,h,w,co]·x[n, h+kh−p, w+kw−p, ci]  (OIHW)"""
+    p = k // 2
+    Cin, Cout = x.shape[-1], dy.shape[-1]
+    dw = torch.zeros(Cout, Cin, k, k, dtype=x.dtype, device=x.device)
+    a = torch.zeros_like(dw)
+    g = dy.reshape(-1, Cout)
+    for kh in range(k):
+        for kw in range(k):
+            xs = _shifted(x, kh - p, kw - p).reshape(-1, Cin)
+            dw[:, :, kh, kw] = g.T @ xs
+            a[:, :, kh, kw] = g.abs().T @ xs.abs()
+    return NS(dw=dw, abs_terms=a)
+
+
+def convt_k2s2(x, w4, bias=None):
+    """ConvTranspose2d(k=2, s=2) in the UNET_OUT_SHUFFLE2 convention: the 1x1 conv w4 [4·Ct, Cin, 1, 1] of x
+    [N,H,W,Cin], whose output channel (2a+b)·Ct + c of pixel (y, x) lands at out[n, 2y+a, 2x+b, c] (+ bias[c])"""
+    N, H, W, _ = x.shape
+    Ct = w4.shape[0] // 4
+    r = conv_fwd(x, w4, 1)
+
+    def shuffle(t):
+        return t.reshape(N, H, W, 2, 2, Ct).permute(0, 1, 3, 2, 4, 5).reshape(N, 2 * H, 2 * W, Ct)
+
+    out, a = shuffle(r.y), shuffle(r.abs_terms)
+    if bias is not None:
+        out, a = out + bias.to(out.dtype), a + bias.to(out.dtype).abs()
+    return NS(out=out, abs_terms=a)
+
+
+def convt_weight4(wt):
+    """nn.ConvTranspose2d weight [Cin, Ct, 2, 2] -> the equivalent 1x1 weight [4·Ct, Cin, 1, 1]"""
+    Cin, Ct = wt.shape[:2]
+    return wt.permute(2, 3, 1, 0).reshape(4 * Ct, Cin, 1, 1)
+
+
+def conv_input(srcs, N, H, W, dtype):
+    """The conv's concatenated input [N,H,W,ΣC] in fp64 from unet_src-like specs: each an NS / dict with kind
+    ('plain', 'act', 'pool_act', 'up_act', 'up_plain', 'nchw'), x (the stored tensor; [N,C,H,W] for nchw) and, by
+    kind, scale, shift, relu, gate_p, gate_ab, up = (up_h, up_w, pad_t, pad_l).  Each source is materialised by the
+    references above (zero outside a placed map) and rounded once to the op dtype, as the kernels stage it."""
+    parts = []
+    for s in srcs:
+        s = s if isinstance(s, dict) else vars(s)
+        if s["kind"] == "nchw":
+            v = d(s["x"]).permute(0, 2, 3, 1)
+        else:
+            v = materialize(s["kind"], s["x"], H, W, s.get("scale"), s.get("shift"), s.get("relu", 0),
+                            s.get("gate_p"), s.get("gate_ab"), s.get("up")).out
+        assert tuple(v.shape[:3]) == (N, H, W), (s["kind"], tuple(v.shape))
+        parts.append(v.to(dtype).double())
+    return torch.cat(parts, -1)
+
+
+def conv_stats(y):
+    """BN partial-sum expectations of the y epilogue: Σy, Σy² per channel from the unrounded y (the header's "from
+    the fp32 accumulators") and the sums of their absolute terms"""
+    y2 = y.reshape(-1, y.shape[-1])
+    return NS(sum=y2.sum(0), sumsq=(y2 * y2).sum(0), abs_sum=y2.abs().sum(0), abs_sumsq=(y2 * y2).sum(0))
+
+
+def conv_bnb(g_stored, bnb_y, scale, shift, relu, mean, invstd):
+    """the bnb_* sums of a dgrad's y epilogue (unet_conv_desc): g = out as stored where relu?(bnb_y·scale+shift) > 0,
+    Σg and Σg·(bnb_y − mean)·invstd.  abs_gx bounds the distributed form too: Σ|g|·(|y| + |mean|)·invstd"""
+    C = g_stored.shape[-1]
+    r = bn_bwd_sums(g_stored.reshape(-1, C), bnb_y.reshape(-1, C), scale, shift, relu, mean, invstd)
+    r.abs_gx = (r.g.abs() * (d(bnb_y).reshape(-1, C).abs() + d(mean).abs()) * d(invstd).abs()).sum(0)
+    return r
+
+
+def pool_bwd(g, code, Hs, Ws, old=None):
+    """MaxPool2d(2) backward: g [N,H,W,C] added at the window position code (0..3, row-major) selects, into a
+    [N,Hs,Ws,C] map (Hs >= 2H, Ws >= 2W; rows / columns past the windows keep `old`)"""
+    N, H, W, C = g.shape
+    out = torch.zeros(N, Hs, Ws, C, dtype=torch.float64, device=g.device) if old is None else d(old).clone()
+    for q in range(4):
+        out[:, (q >> 1):2 * H:2, (q & 1):2 * W:2] += torch.where(code == q, d(g), torch.zeros_like(d(g)))
+    return out
+
+
+# ---- the exact-grid method ---------------------------------------------------------------------------
+# Operands drawn on a dyadic grid make every product a multiple of one unit u.  Where Σ|terms| / u < 2^24 for an
+# output element, every partial sum of those terms, in any order and any split, is an integer multiple of u below
+# 2^24·u and so exactly representable in fp32: a kernel that accumulates in fp32 must return the fp64 value itself.
+
+EXACT_CAP = float(2 ** 24)
+
+
+def grid(shape, step, kmax, dtype, generator, device="cpu"):
+    """k·step with k uniform on the integers [−kmax, kmax] (kmax·step and step must be exact in dtype)"""
+    k = torch.randint(-kmax, kmax + 1, tuple(shape), generator=generator, device=generator.device)
+    v = (k.double() * step).to(dtype)
+    assert torch.equal(v.double(), k.double() * step), "grid not representable in the dtype"
+    return v.to(device)
+
+
+def exact_units(abs_terms, unit):
+    """the largest Σ|terms| / unit over the outputs: below 2^24 every fp32 partial sum is exact"""
+    return float(abs_terms.max() / unit) if abs_terms.numel() else 0.0
+
+
+def check_exact(got, ref64, dtype, what, names=("n", "h", "w", "c"), mods=(0, 16, 32, 16)):
+    """got must be ref64 rounded once (to nearest even) to dtype, bit for bit apart from the sign of zero.  On a
+    mismatch: how many, the first wrong index, expected and got there, and the residues of the wrong indices
+    (h mod 16, w mod 32, c mod 16 for an NHWC map), which name the tile edge, tap or channel fragment at fault."""
+    r32 = ref64.to(torch.float32)
+    assert torch.equal(r32.double(), ref64), (what, "the reference is not exact in fp32: the exactness condition fails")
+    want = r32.to(dtype)
+    got = got.reshape(want.shape)
+    assert got.dtype == dtype, (what, got.dtype, dtype)
+    if torch.equal(got, want):
+        return
+    bad = (got != want) | got.isnan()
+    idx = bad.nonzero()
+    first = tuple(int(i) for i in idx[0])
+    res = {}
+    for dim, (nm, m) in enumerate(zip(names, mods)):
+        if m and dim < idx.shape[1]:
+            res[f"{nm}%{m}"] = sorted(set((idx[:, dim] % m).tolist()))
+    raise AssertionError(f"{what}: {int(bad.sum())} of {bad.numel()} wrong; first at {dict(zip(names, first))}: "
+                         f"expected {float(want[first])!r}, got {float(got[first])!r}; residues {res}")

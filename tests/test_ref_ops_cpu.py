@@ -357,3 +357,192 @@ def test_materialize_kinds_and_layouts():
     one = torch.tensor([1.0, 0.99, 0.0], dtype=torch.float64)
     assert RO.ulp(one, torch.bfloat16).tolist() == [2.0 ** -7, 2.0 ** -8, 2.0 ** -133]
     assert RO.ulp(one, torch.float16).tolist() == [2.0 ** -10, 2.0 ** -11, 2.0 ** -24]
+
+
+# ---- convolutions and the exact-grid method ----------------------------------------------------------
+
+CONV_REF_SHAPES = [(2, 5, 7, 5, 6, 3), (1, 4, 9, 20, 3, 1), (3, 6, 4, 7, 33, 3), (1, 1, 3, 4, 2, 3), (2, 9, 5, 33, 17, 1)]
+
+
+def _conv_operands(shape, seed):
+    N, H, W, Cin, Cout, k = shape
+    g = torch.Generator().manual_seed(seed)
+    x = torch.randn(N, H, W, Cin, generator=g, dtype=torch.float64)
+    w = torch.randn(Cout, Cin, k, k, generator=g, dtype=torch.float64)
+    dy = torch.randn(N, H, W, Cout, generator=g, dtype=torch.float64)
+    return x, w, dy
+
+
+def test_conv_references_match_torch():
+    """conv_fwd / conv_dgrad / conv_wgrad (shifted matrix products) against fp64 F.conv2d, F.conv_transpose2d and
+    torch.nn.grad.conv2d_weight: non-square maps, channel counts off every multiple of 16, k = 1 and 3"""
+    for i, shape in enumerate(CONV_REF_SHAPES):
+        x, w, dy = _conv_operands(shape, 40 + i)
+        k, p = shape[-1], shape[-1] // 2
+        xc, dyc = x.permute(0, 3, 1, 2), dy.permute(0, 3, 1, 2)
+        r = RO.conv_fwd(x, w, k)
+        _close(r.y, F.conv2d(xc, w, padding=p).permute(0, 2, 3, 1), ("fwd", shape))
+        _close(r.abs_terms, F.conv2d(xc.abs(), w.abs(), padding=p).permute(0, 2, 3, 1), ("fwd abs", shape))
+        r = RO.conv_dgrad(dy, w, k)
+        _close(r.dx, F.conv_transpose2d(dyc, w, padding=p).permute(0, 2, 3, 1), ("dgrad", shape))
+        _close(r.abs_terms, F.conv_transpose2d(dyc.abs(), w.abs(), padding=p).permute(0, 2, 3, 1), ("dgrad abs", shape))
+        r = RO.conv_wgrad(x, dy, k)
+        _close(r.dw, torch.nn.grad.conv2d_weight(xc, w.shape, dyc, padding=p), ("wgrad", shape))
+        _close(r.abs_terms, torch.nn.grad.conv2d_weight(xc.abs(), w.shape, dyc.abs(), padding=p), ("wgrad abs", shape))
+        # the three are one bilinear form: <dy, conv(x, w)> = <x, dgrad(dy, w)> = <w, wgrad(x, dy)>
+        s = (dy * RO.conv_fwd(x, w, k).y).sum()
+        _close((x * RO.conv_dgrad(dy, w, k).dx).sum(), s, ("adjoint dx", shape), 1e-11)
+        _close((w * RO.conv_wgrad(x, dy, k).dw).sum(), s, ("adjoint dw", shape), 1e-11)
+
+
+def test_convt_k2s2_matches_torch():
+    g = torch.Generator().manual_seed(50)
+    for N, H, W, Cin, Ct in ((2, 3, 5, 6, 4), (1, 4, 2, 5, 3)):
+        x = torch.randn(N, H, W, Cin, generator=g, dtype=torch.float64)
+        wt = torch.randn(Cin, Ct, 2, 2, generator=g, dtype=torch.float64)
+        b = torch.randn(Ct, generator=g, dtype=torch.float64)
+        for bias in (b, None):
+            r = RO.convt_k2s2(x, RO.convt_weight4(wt), bias)
+            ref = F.conv_transpose2d(x.permute(0, 3, 1, 2), wt, bias, stride=2).permute(0, 2, 3, 1)
+            _close(r.out, ref, ("convt", N, H, W, bias is None))
+            ra = F.conv_transpose2d(x.permute(0, 3, 1, 2).abs(), wt.abs(), None if bias is None else b.abs(), stride=2)
+            _close(r.abs_terms, ra.permute(0, 2, 3, 1), ("convt abs", N, H, W))
+
+
+def test_conv_input_concat_with_placed_map():
+    """a gated BN activation next to the padded bilinear up-sampling of another, rounded to the op dtype, against
+    plain torch; then through conv_fwd against F.conv2d of the same concat"""
+    g = torch.Generator().manual_seed(51)
+    N, H, W, C0, C1 = 2, 7, 10, 5, 6
+    y0 = torch.randn(N, H, W, C0, generator=g).bfloat16()
+    y1 = torch.randn(N, 3, 4, C1, generator=g).bfloat16()
+    ab0, ab1 = torch.randn(2, C0, generator=g), torch.randn(2, C1, generator=g)
+    p, pab = torch.randn(N, H, W, generator=g), torch.tensor([0.7, -0.2])
+    up = (5, 7, 1, 2)
+    srcs = [dict(kind="act", x=y0, scale=ab0[0], shift=ab0[1], relu=1, gate_p=p, gate_ab=pab),
+            dict(kind="up_act", x=y1, scale=ab1[0], shift=ab1[1], relu=0, up=up)]
+    x = RO.conv_input(srcs, N, H, W, torch.bfloat16)
+    a0 = (y0.double() * ab0[0].double() + ab0[1].double()).clamp_min(0)
+    a0 = a0 * torch.sigmoid(p.double() * pab[0].double() + pab[1].double()).unsqueeze(-1)
+    a1 = (y1.double() * ab1[0].double() + ab1[1].double()).permute(0, 3, 1, 2)
+    a1 = F.interpolate(a1, size=up[:2], mode="bilinear", align_corners=True)
+    a1 = F.pad(a1, [up[3], W - up[1] - up[3], up[2], H - up[0] - up[2]]).permute(0, 2, 3, 1)
+    want = torch.cat([a0, a1], -1).bfloat16().double()
+    assert torch.equal(x, want)
+    assert (x[:, 0, :, C0:] == 0).all() and (x[:, :, :2, C0:] == 0).all()   # zero outside the placed map
+    w = torch.randn(4, C0 + C1, 3, 3, generator=g, dtype=torch.float64)
+    _close(RO.conv_fwd(x, w, 3).y, F.conv2d(want.permute(0, 3, 1, 2), w, padding=1).permute(0, 2, 3, 1), "concat conv")
+    # an NCHW source is transposed, a pooled one is the first-maximum max-pool
+    xn = torch.randn(N, 3, H, W, generator=g)
+    assert torch.equal(RO.conv_input([dict(kind="nchw", x=xn)], N, H, W, torch.float32), xn.double().permute(0, 2, 3, 1))
+    yp = torch.randn(N, 2 * H + 1, 2 * W, C0, generator=g)
+    xp = RO.conv_input([dict(kind="pool_act", x=yp, scale=ab0[0], shift=ab0[1], relu=1)], N, H, W, torch.float32)
+    ap = (yp.double() * ab0[0].double() + ab0[1].double()).clamp_min(0).permute(0, 3, 1, 2)
+    assert torch.equal(xp, F.max_pool2d(ap, 2).permute(0, 2, 3, 1).float().double())
+
+
+def test_conv_stats_bnb_and_pool_bwd():
+    g = torch.Generator().manual_seed(52)
+    y = torch.randn(2, 4, 5, 3, generator=g, dtype=torch.float64)
+    st = RO.conv_stats(y)
+    _close(st.sum, y.sum((0, 1, 2)), "Σy")
+    _close(st.sumsq, (y * y).sum((0, 1, 2)), "Σy²")
+    by = torch.randn(2, 4, 5, 3, generator=g, dtype=torch.float64)
+    sc, sf, mu, iv = (torch.randn(3, generator=g, dtype=torch.float64) for _ in range(4))
+    b = RO.conv_bnb(y, by, sc, sf, 1, mu, iv)
+    m = (by * sc + sf > 0).double()
+    _close(b.sum_g, (y * m).sum((0, 1, 2)), "Σg")
+    _close(b.sum_gx, (y * m * (by - mu) * iv).sum((0, 1, 2)), "Σg·x̂")
+    assert (b.abs_gx >= b.sum_gx.abs()).all()
+    # pool_bwd with the reference's own codes is autograd's max_pool2d backward (no ties in random data)
+    a = torch.randn(2, 9, 10, 3, generator=g, dtype=torch.float64)
+    code = RO.maxpool_act(a, None, None, 0, 4, 5).code
+    gp = torch.randn(2, 4, 5, 3, generator=g, dtype=torch.float64)
+    old = torch.randn(2, 9, 10, 3, generator=g, dtype=torch.float64)
+    ac = a.permute(0, 3, 1, 2).clone().requires_grad_(True)
+    F.max_pool2d(ac, 2).backward(gp.permute(0, 3, 1, 2))
+    _close(RO.pool_bwd(gp, code, 9, 10, old), ac.grad.permute(0, 2, 3, 1) + old, "pool_bwd")
+
+
+def _emulate(x, w, k, dtype, order_seed, splits, mutate=None, kc=8):
+    """A correct kernel on the CPU: the k·k·ceil(Cin / kc) chunk products of a 'same' conv, accumulated in fp32 in
+    a shuffled order into `splits` slabs that are then added in fp32, and rounded once to dtype (nearest even).
+    mutate: one of the five subtle errors the exact gate must reject."""
+    N, H, W, Cin = x.shape
+    Cout, p = w.shape[0], k // 2
+    xf, wf = x.float(), w.float()
+    if mutate == "last_channel":
+        xf = xf.clone()
+        xf[..., Cin - 1] = 0
+    chunks = [(kh, kw, c0) for kh in range(k) for kw in range(k) for c0 in range(0, Cin, kc)]
+    order = torch.randperm(len(chunks), generator=torch.Generator().manual_seed(order_seed)).tolist()
+    slabs = [torch.zeros(N, H, W, Cout) for _ in range(splits)]
+    for j, ci in enumerate(order):
+        kh, kw, c0 = chunks[ci]
+        xs = RO._shifted(xf, kh - p, kw - p)
+        if mutate == "halo_row" and (kh, kw) == (0, 1):   # pixel (0, 2, 3) reads its upper neighbour from its own row
+            xs = xs.clone()
+            xs[0, 2, 3] = xf[0, 2, 3]
+        t = xs[..., c0:c0 + kc] @ wf[:, c0:c0 + kc, kh, kw].T
+        if mutate == "drop_tap" and (kh, kw) == (1, 2):   # the right-hand tap of border pixel (0, 0, 2)
+            t[0, 0, 2] = 0
+        slabs[j % splits] += t
+    if mutate == "slab_twice":
+        slabs[0][0, 3, 1] *= 2
+    acc = slabs[0]
+    for s in slabs[1:]:
+        acc = acc + s
+    if mutate == "truncate" and dtype != torch.float32:
+        bits = 16
+        return acc, (acc.view(torch.int32) >> bits << bits).view(torch.float32).to(dtype)
+    return acc, acc.to(dtype)
+
+
+def test_exact_gate_is_sharp():
+    """On grid operands a correct kernel — any chunk order, 1-, 2- or 8-way split-K — equals fp64 bit for bit, and each
+    of five one-term errors is rejected, in the fp32 accumulator and in the rounded 16-bit output"""
+    g = torch.Generator().manual_seed(53)
+    N, H, W, Cin, Cout, k = 1, 6, 7, 20, 12, 3
+    x = RO.grid((N, H, W, Cin), 0.25, 12, torch.bfloat16, g).double()
+    w = RO.grid((Cout, Cin, k, k), 0.125, 4, torch.float32, g).double()
+    ref = RO.conv_fwd(x, w, k)
+    assert RO.exact_units(ref.abs_terms, 0.25 * 0.125) < 2 ** 22
+    assert ((ref.y.float().to(torch.bfloat16).double() - ref.y) != 0).any()        # the rounding is exercised,
+    tie = (ref.y.abs() * 32).to(torch.int64)                                          # ... with ties among it
+    assert ((ref.y.abs() >= 8) & (ref.y.abs() < 16) & (tie % 4 == 2)).any()
+    for seed in range(3):
+        for splits in (1, 2, 8):
+            acc, out = _emulate(x, w, k, torch.bfloat16, seed, splits)
+            RO.check_exact(acc, ref.y, torch.float32, "accumulator")
+            RO.check_exact(out, ref.y, torch.bfloat16, "bf16 output")
+    for mutate in ("drop_tap", "last_channel", "halo_row", "slab_twice", "truncate"):
+        acc, out = _emulate(x, w, k, torch.bfloat16, 0, 2, mutate)
+        for got, dt in ((acc, torch.float32), (out, torch.bfloat16)):
+            if mutate == "truncate" and dt == torch.float32:
+                continue
+            try:
+                RO.check_exact(got, ref.y, dt, mutate)
+            except AssertionError as e:
+                msg = str(e)
+                assert "wrong; first at" in msg and "h%16" in msg and "c%16" in msg, msg
+                if mutate == "drop_tap":
+                    assert "'h': 0, 'w': 2" in msg and "'w%32': [2]" in msg, msg
+                if mutate == "slab_twice":
+                    assert "'h': 3, 'w': 1" in msg, msg
+            else:
+                raise AssertionError(f"the exact gate passed the mutation {mutate} ({dt})")
+
+
+def test_grid_and_exact_units():
+    g = torch.Generator().manual_seed(54)
+    v = RO.grid((1000,), 0.25, 12, torch.bfloat16, g)
+    assert v.dtype == torch.bfloat16 and float(v.abs().max()) == 3.0 and float(v.min()) == -3.0
+    assert torch.equal(v.double() * 4, (v.double() * 4).round())
+    assert (v == 0).any()
+    assert RO.exact_units(torch.tensor([1.0, 8.0]), 0.125) == 64.0
+    try:
+        RO.grid((4,), 1.0 / 1024, 1000, torch.bfloat16, g)
+    except AssertionError:
+        pass
+    else:
+        raise AssertionError("a grid the dtype cannot hold was accepted")

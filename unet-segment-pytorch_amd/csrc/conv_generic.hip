@@ -192,15 +192,19 @@ __global__ __launch_bounds__(NTHR) void conv_generic_kernel(const unet_conv_desc
         for (int r = 0; r < 4; ++r) {
           const int ow = ow_base + r;
           if (oh < d.H && ow < d.W && co < d.Cout) {
-            const float sc = ps.scale[co], sf = ps.shift[co];
-            float best = -INFINITY;
             int bq = 0;
+            if (d.pool_code) {  // the argmax recorded by unet_materialize_pool routes, as in conv2 / conv3
+              bq = d.pool_code[((n * d.H + oh) * (long long)d.W + ow) * d.Cout + co] & 3;
+            } else {
+              const float sc = ps.scale[co], sf = ps.shift[co];
+              float best = -INFINITY;
 #pragma unroll
-            for (int q = 0; q < 4; ++q) {
-              const long long sp = (n * ps.H + 2 * oh + (q >> 1)) * (long long)ps.W + 2 * ow + (q & 1);
-              float a = __builtin_fmaf(to_f(ysrc[sp * d.Cout + co]), sc, sf);
-              if (ps.relu) a = fmaxf(a, 0.f);
-              if (a > best || a != a) { best = a; bq = q; }
+              for (int q = 0; q < 4; ++q) {
+                const long long sp = (n * ps.H + 2 * oh + (q >> 1)) * (long long)ps.W + 2 * ow + (q & 1);
+                float a = __builtin_fmaf(to_f(ysrc[sp * d.Cout + co]), sc, sf);
+                if (ps.relu) a = fmaxf(a, 0.f);
+                if (a > best || a != a) { best = a; bq = q; }
+              }
             }
             const long long sp = (n * ps.H + 2 * oh + (bq >> 1)) * (long long)ps.W + 2 * ow + (bq & 1);
             da[sp * d.Cout + co] += acc[i][j][r];

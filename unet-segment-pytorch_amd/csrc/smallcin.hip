@@ -230,8 +230,12 @@ __global__ __launch_bounds__(256) void smallcin_wgrad_kernel(const unet_wgrad_de
   const T* dy = (const T*)d.dy;
   const int G = d.Cout / 8;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  // every wave covers all G co groups: lane -> (pixel slot, group)
-  const int lanes_per_px = G <= 64 ? G : 64;
+  // every wave covers all G co groups: lane -> (pixel slot, group).  The lanes of a pixel are a power of two (the
+  // butterfly below adds lanes lanes_per_px, 2·lanes_per_px, ... apart, and 64 / lanes_per_px slots must tile the
+  // wave): G rounded up, the lanes with g0 >= G idle.  (With lanes_per_px = G, Cout = 40 gave 12 slots of 5 lanes
+  // plus 4 lanes on a 13th slot that the next wave also covers, and a sum over the wrong lanes.)
+  int lanes_per_px = 1;
+  while (lanes_per_px < G && lanes_per_px < 64) lanes_per_px <<= 1;
   const int g0 = lane % lanes_per_px, ps = lane / lanes_per_px, PPW = 64 / lanes_per_px;
   const long long P = (long long)d.N * d.H * d.W;
   const long long per = (P + rows - 1) / rows;
@@ -276,7 +280,7 @@ __global__ __launch_bounds__(256) void smallcin_wgrad_kernel(const unet_wgrad_de
           for (int o = lanes_per_px; o < 64; o <<= 1) a += __shfl_xor(a, o, 64);
           acc[j][t] = a;
         }
-      for (int gg = 0; gg < lanes_per_px; ++gg) {
+      for (int gg = 0; gg < lanes_per_px && gbase + gg < G; ++gg) {   // (block-uniform: skips the padded groups)
         if (ps == 0 && g0 == gg) {
 #pragma unroll
           for (int j = 0; j < 8; ++j)
