@@ -273,9 +273,10 @@ int unet_upsample_bwd(long long N, int C, int Hs, int Ws, int up_h, int up_w, in
  * channels; dgw op dtype NHWC [N,Hp,Wp,Ci], wt_packed = unet_pack_weight(W_g, transpose=1)) is
  * formed as d_up is loaded instead of by an accumulating UNET_OUT_F32 unet_conv into d_up first.
  * d_up is not written.  dx has the bits of those two calls where the conv runs on the 1x1 MFMA
- * kernel (unet_conv_variant "pw_conv_kernel...").  _ok: whether the geometry is served (16-bit
- * dtype, C % 64 == 0, Ci in {32, 64, 128, 256}, the tiled adjoint's window limits); the call
- * fails otherwise                                                                                */
+ * kernel (unet_conv_variant "pw_conv_kernel...") and unet_upsample_bwd on its tiled kernel (every
+ * map of more than 8 rows and columns that _ok admits).  _ok: whether the geometry is served
+ * (16-bit dtype, C % 64 == 0, Ci in {32, 64, 128, 256}, the tiled adjoint's window limits, a
+ * window counted as at most the whole map); the call fails otherwise                             */
 int unet_upsample_bwd_pw_ok(int dtype, long long N, int C, int Hs, int Ws, int up_h, int up_w, int pad_t,
                             int pad_l, int Hp, int Wp, float sh, float sw, int Ci);
 int unet_upsample_bwd_pw(int dtype, long long N, int C, int Hs, int Ws, int up_h, int up_w, int pad_t,

@@ -232,45 +232,47 @@ __device__ __forceinline__ uint4 upb_ld(upb_rsrc_t r, unsigned voff, unsigned so
 // per destination pixel and channel, i.e. pw_conv_kernel's MFMA chain from a zero accumulator and its OMK == 1
 // epilogue's one fp32 add, then the fmaf steps, LDS tile and phase 2 of upsample_bwd_tile_kernel: the result has the
 // bits of the two launches, and d_up is read once instead of read, written and read.
-//  The block tile is upsample_bwd_tile_kernel's (one source row, UPB_J source columns, 64 channels).  A wave owns
-//  WA of the block's four 16-channel MFMA tiles, whose NCH weight fragments each (the packed transposed weight,
-//  the A operand) stay in registers, and walks the window's destination columns 16 at a time: lane (i16, g) holds
-//  column 16 grp + i16; its B operand is one 16-byte load of dgw channels 32 c + 8 g .. + 7 of that pixel, its
+//  A block owns R consecutive source rows, J source columns and 64 channels, and walks the union of its rows'
+//  destination windows (2R + 2 live rows of a x2 map, where R one-row blocks walked 4R) once, in ascending order:
+//    v formed once per destination pixel;  a[r] = fmaf(w(u, r), v, a[r]) for the (at most two) owned rows u feeds.
+//  Each owned row's accumulator starts at +0 and takes its live destination rows in ascending order with the
+//  weights of upsample_bwd_tile_kernel's wy[] expression.  A slot of weight 0 adds fmaf(0, x, a) = a there (a starts
+//  as +0 and a fused multiply-add into +0 or a non-zero sum never yields -0), so leaving those slots out keeps every
+//  bit: the chain of every (row, column, channel) is that kernel's.  Phase 2 is its phase 2, per owned row; neither J
+//  nor R enters any sum.
+//  A wave owns WA of the block's four 16-channel MFMA tiles, whose NCH weight fragments each (the packed transposed
+//  weight, the A operand) stay in registers, and walks the window's destination columns 16 at a time: lane (i16, g)
+//  holds column 16 grp + i16; its B operand is one 16-byte load of dgw channels 32 c + 8 g .. + 7 of that pixel, its
 //  accumulator the float4 of channels 16 tile + 4 g .. + 3, the granularity of d_up's loads and of the LDS tile.
-//  Only the window rows with a non-zero weight are walked (compacted, see below).
-template <typename T, int NCH, int WA>
-__global__ __launch_bounds__(256, 4) void upsample_bwd_pw_kernel(int N, int C, int Hs, int Ws, int up_h, int up_w, int pt,
-                                                              int pl, int Hp, int Wp, float sh, float sw,
-                                                              const float* __restrict__ dup,
-                                                              const uint4* __restrict__ dgw,
-                                                              const uint4* __restrict__ wt, float* dx, int accum,
-                                                              int ntj, int ntc) {
+//  Row table: lane l of every wave evaluates destination row U0 + l of the window against the R owned rows; the
+//  rows that feed an owned row are a ballot mask walked bit by bit, a row's weights read from its lane
+//  (block-uniform scalars).  Rows of the last group past Hs have weight 0 everywhere and store nothing.
+//  Loads: RB live rows are one stage; the next stage's loads are issued before the MFMAs and fmafs of the current
+//  one.  Weight fragments, the column table and the row table are set up once per block.
+//  OCC: waves per SIMD the register allocation is held to.
+template <typename T, int NCH, int WA, int R, int J, int RB, int OCC>
+__global__ __launch_bounds__(256, OCC) void upsample_bwd_pw_kernel(
+    int N, int C, int Hs, int Ws, int up_h, int up_w, int pt, int pl, int Hp, int Wp, float sh, float sw,
+    const float* __restrict__ dup, const uint4* __restrict__ dgw, const uint4* __restrict__ wt, float* dx, int accum,
+    int ntj, int ntc) {
   typedef typename Mma<T>::frag F;
-  // (rows padded by one vector: phase 1 writes a column per lane, 16 rows per 16-lane pass; at the unpadded
-  // 256-byte row stride those 16 writes fell on the same banks)
-  __shared__ float4 t[UPB_VMAX][UPB_CT + 1];
+  __shared__ float4 t[R][UPB_VMAX][UPB_CT + 1];
   __shared__ int tab_i0[UPB_VMAX], tab_i1[UPB_VMAX];
   __shared__ float tab_l[UPB_VMAX];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, i16 = lane & 15, g = lane >> 4;
   const unsigned lb = xcd_block(blockIdx.x, gridDim.x);
   const int ct = (int)(lb % (unsigned)ntc);
-  unsigned r = lb / (unsigned)ntc;
-  const int jt = (int)(r % (unsigned)ntj);
-  r /= (unsigned)ntj;
-  const int i = (int)(r % (unsigned)Hs);
-  const int n = (int)(r / (unsigned)Hs);
-  const int C4 = C >> 2;   // (host-checked: C % 64 == 0, every channel tile is whole)
-  const int j0 = jt * UPB_J;
-  const int ulo = max(0, (int)ceilf((float)(i - 1) / sh) - 1), uhi = min(up_h - 1, (int)floorf((float)(i + 1) / sh) + 1);
-  float wy[8];
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    const int u = ulo + k, yy = u + pt;
-    wy[k] = (u <= uhi && yy >= 0 && yy < Hp) ? up_weight(sh, u, Hs, i) : 0.f;
-  }
-  const int jlast = min(Ws - 1, j0 + UPB_J - 1);
+  unsigned rr = lb / (unsigned)ntc;
+  const int jt = (int)(rr % (unsigned)ntj);
+  rr /= (unsigned)ntj;
+  const unsigned ngr = ((unsigned)Hs + R - 1) / R;
+  const int ibase = (int)(rr % ngr) * R;
+  const int n = (int)(rr / ngr);
+  const int C4 = C >> 2;
+  const int j0 = jt * J;
+  const int jlast = min(Ws - 1, j0 + J - 1);
   const int vlo = max(0, (int)ceilf((float)(j0 - 1) / sw) - 1), vhi = min(up_w - 1, (int)floorf((float)(jlast + 1) / sw) + 1);
-  const int nv = vhi - vlo + 1;
+  const int nv = vhi - vlo + 1;   // (host-checked <= UPB_VMAX)
   if (tid < nv) {
     const int v = vlo + tid, xx = v + pl;
     int a0, a1;
@@ -281,9 +283,21 @@ __global__ __launch_bounds__(256, 4) void upsample_bwd_pw_kernel(int N, int C, i
     tab_i1[tid] = ok ? a1 : -1;
     tab_l[tid] = l;
   }
-  // this wave's weight fragments: packed [C / 16 tiles (padded)][NCH][64 lanes] x 16 bytes
-  // (WA: 16-channel tiles per wave.  The 4 / WA waves that share a column group cover the block's 64 channels;
-  // the WA sets of such waves take the column groups in turn)
+  // the row table (host-checked: the group's window spans <= 64 destination rows)
+  const int U0 = max(0, (int)ceilf((float)(ibase - 1) / sh) - 1);
+  float wr[R];
+  bool feeds = false;
+  {
+    const int u = U0 + lane, yy = u + pt;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      const int i = ibase + r;
+      const int ulo = max(0, (int)ceilf((float)(i - 1) / sh) - 1), uhi = min(up_h - 1, (int)floorf((float)(i + 1) / sh) + 1);
+      wr[r] = (i < Hs && u >= ulo && u <= uhi && yy >= 0 && yy < Hp) ? up_weight(sh, u, Hs, i) : 0.f;
+      feeds = feeds || wr[r] != 0.f;
+    }
+  }
+  const unsigned long long live = __ballot(feeds);
   const int wa = wave % (4 / WA), wg = wave / (4 / WA);
   F wq[WA][NCH];
 #pragma unroll
@@ -291,136 +305,161 @@ __global__ __launch_bounds__(256, 4) void upsample_bwd_pw_kernel(int N, int C, i
 #pragma unroll
     for (int c = 0; c < NCH; ++c)
       wq[aa][c] = __builtin_bit_cast(F, wt[((size_t)(ct * 4 + wa * WA + aa) * NCH + c) * 64 + lane]);
-  // phase 1: one column and WA channel vectors per lane and trip, the vectors 4 (wa WA + aa) + g of the block's 16
   const int cl = 4 * wa * WA + g;
-  // image n of d_up and of dgw as raw buffers: a row of the window is a block-uniform scalar offset, a lane's
-  // column and channels one 32-bit offset for all rows (no 64-bit address per load); lanes without a column
-  // read zeros through the out-of-range offset
   const size_t img = (size_t)Hp * Wp;
   const upb_rsrc_t dr = upb_rsrc(dup + (size_t)n * img * C, (unsigned)(img * C * 4));
   const upb_rsrc_t xr = upb_rsrc(dgw + (size_t)n * img * (4 * NCH), (unsigned)(img * (64 * NCH)));
-  // the window rows with a non-zero weight, compacted in order (block-uniform scalars).  A zero-weight slot adds
-  // fmaf(0, 0, a) = a in upsample_bwd_tile_kernel (a starts as +0 and a fused multiply-add into +0 or a non-zero
-  // sum never yields -0), so leaving those slots out keeps every bit; a x2 window has 4, rarely 5, live rows of 8
-  int nlive = 0, pos[8];
-#pragma unroll
-  for (int k = 0; k < 8; ++k) pos[k] = wy[k] != 0.f ? nlive++ : -1;
-  float wl[8];
-  unsigned rowd[8], rowx[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    wl[j] = 0.f;
-    unsigned row = 0u;
-#pragma unroll
-    for (int k = 0; k < 8; ++k)   // wy[k] != 0: ulo + k <= uhi and 0 <= ulo + k + pt < Hp
-      if (pos[k] == j) { wl[j] = wy[k]; row = (unsigned)(ulo + k + pt) * (unsigned)Wp; }
-    rowd[j] = row * (unsigned)C * 4u;
-    rowx[j] = row * (unsigned)(64 * NCH);
-  }
   const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
+  // phase 1: one column and WA channel vectors per lane; the wave's column groups in turn
   for (int it = 16 * wg + i16; it - i16 < nv; it += 16 * WA) {
     const int xx = vlo + it + pl;
     const bool ok = it < nv && xx >= 0 && xx < Wp;
     const unsigned dvo = ok ? (unsigned)xx * (unsigned)C * 4u + (unsigned)(ct * UPB_CT + cl) * 16u : UPB_OOB;
     const unsigned xvo = ok ? (unsigned)xx * (unsigned)(64 * NCH) + (unsigned)g * 16u : UPB_OOB;
-    float4 a[WA];
+    float4 a[R][WA];
 #pragma unroll
-    for (int aa = 0; aa < WA; ++aa) a[aa] = z4;
-    // live rows four at a time: 4 (1 + NCH) independent 16-byte loads per lane and batch; slots past the last
-    // live row read zeros (out-of-range offset) and add fmaf(0, 0, a)
+    for (int r = 0; r < R; ++r)
 #pragma unroll
-    for (int k0 = 0; k0 < 8; k0 += 4) {
-      if (k0 && nlive <= 4) break;
-      float4 dv[WA][4];
-      f32x4 acc[WA][4];
-      unsigned dvk[4], xvk[4];
+      for (int aa = 0; aa < WA; ++aa) a[r][aa] = z4;
+    // a stage: RB live rows (slot < 0: none left, the loads read zeros and nothing is added)
+    float4 dv[RB][WA], dvn[RB][WA];
+    uint4 q[RB][NCH], qn[RB][NCH];
+    int sl[RB], sln[RB];
+    unsigned long long m = live;
+#define UPB_STAGE_LOAD(DV, Q, SL)                                                                                   \
+  _Pragma("unroll") for (int k = 0; k < RB; ++k) {                                                              \
+    SL[k] = m ? (int)__builtin_ctzll(m) : -1;                                                                       \
+    m &= m - 1ull;                                                                                                  \
+    const unsigned row = SL[k] < 0 ? 0u : (unsigned)(U0 + SL[k] + pt) * (unsigned)Wp;                               \
+    const unsigned dk = SL[k] < 0 ? UPB_OOB : dvo, xk = SL[k] < 0 ? UPB_OOB : xvo;                                  \
+    _Pragma("unroll") for (int aa = 0; aa < WA; ++aa)                                                               \
+        DV[k][aa] = __builtin_bit_cast(float4, upb_ld(dr, dk, row * (unsigned)C * 4u + (unsigned)aa * 64u));        \
+    _Pragma("unroll") for (int c = 0; c < NCH; ++c)                                                                 \
+        Q[k][c] = upb_ld(xr, xk, row * (unsigned)(64 * NCH) + (unsigned)c * 64u);                                   \
+  }
+    UPB_STAGE_LOAD(dv, q, sl)
+    while (sl[0] >= 0) {
+      UPB_STAGE_LOAD(dvn, qn, sln)
 #pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const bool live = k0 + k < nlive;   // block-uniform
-        dvk[k] = live ? dvo : UPB_OOB;
-        xvk[k] = live ? xvo : UPB_OOB;
+      for (int k = 0; k < RB; ++k) {
+        if (sl[k] < 0) continue;   // block-uniform
+        f32x4 acc[WA];
+#pragma unroll
+        for (int aa = 0; aa < WA; ++aa) acc[aa] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int c = 0; c < NCH; ++c)
+#pragma unroll
+          for (int aa = 0; aa < WA; ++aa) acc[aa] = Mma<T>::mma(wq[aa][c], __builtin_bit_cast(F, q[k][c]), acc[aa]);
+        float4 v[WA];
 #pragma unroll
         for (int aa = 0; aa < WA; ++aa) {
-          dv[aa][k] = __builtin_bit_cast(float4, upb_ld(dr, dvk[k], rowd[k0 + k] + (unsigned)aa * 64u));
-          acc[aa][k] = f32x4{0.f, 0.f, 0.f, 0.f};
-        }
-      }
-#pragma unroll
-      for (int c = 0; c < NCH; ++c) {
-        uint4 q[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) q[k] = upb_ld(xr, xvk[k], rowx[k0 + k] + (unsigned)c * 64u);
-#pragma unroll
-        for (int aa = 0; aa < WA; ++aa)
-#pragma unroll
-          for (int k = 0; k < 4; ++k)
-            acc[aa][k] = Mma<T>::mma(wq[aa][c], __builtin_bit_cast(F, q[k]), acc[aa][k]);
-      }
-#pragma unroll
-      for (int aa = 0; aa < WA; ++aa)
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
           // pw_conv_kernel's accumulating fp32 epilogue: v = acc; v += old
-          float4 v = make_float4(acc[aa][k][0], acc[aa][k][1], acc[aa][k][2], acc[aa][k][3]);
-          v.x += dv[aa][k].x; v.y += dv[aa][k].y; v.z += dv[aa][k].z; v.w += dv[aa][k].w;
-          const float w = wl[k0 + k];
-          a[aa].x = __builtin_fmaf(w, v.x, a[aa].x); a[aa].y = __builtin_fmaf(w, v.y, a[aa].y);
-          a[aa].z = __builtin_fmaf(w, v.z, a[aa].z); a[aa].w = __builtin_fmaf(w, v.w, a[aa].w);
+          v[aa] = make_float4(acc[aa][0], acc[aa][1], acc[aa][2], acc[aa][3]);
+          v[aa].x += dv[k][aa].x; v[aa].y += dv[k][aa].y; v[aa].z += dv[k][aa].z; v[aa].w += dv[k][aa].w;
         }
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+          const float w = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, wr[r]), sl[k]));
+          if (w == 0.f) continue;   // block-uniform
+#pragma unroll
+          for (int aa = 0; aa < WA; ++aa) {
+            a[r][aa].x = __builtin_fmaf(w, v[aa].x, a[r][aa].x); a[r][aa].y = __builtin_fmaf(w, v[aa].y, a[r][aa].y);
+            a[r][aa].z = __builtin_fmaf(w, v[aa].z, a[r][aa].z); a[r][aa].w = __builtin_fmaf(w, v[aa].w, a[r][aa].w);
+          }
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < RB; ++k) {
+        sl[k] = sln[k];
+#pragma unroll
+        for (int aa = 0; aa < WA; ++aa) dv[k][aa] = dvn[k][aa];
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) q[k][c] = qn[k][c];
+      }
     }
+#undef UPB_STAGE_LOAD
     if (it < nv) {
 #pragma unroll
-      for (int aa = 0; aa < WA; ++aa) t[it][cl + 4 * aa] = a[aa];
+      for (int r = 0; r < R; ++r)
+#pragma unroll
+        for (int aa = 0; aa < WA; ++aa) t[r][it][cl + 4 * aa] = a[r][aa];
     }
   }
   __syncthreads();
-  // phase 2: upsample_bwd_tile_kernel's, one (source column, channel vector) per thread
-  const int j = j0 + (tid >> 4);
-  if (j > jlast) return;
-  const int c4 = ct * UPB_CT + (tid & (UPB_CT - 1));
-  const int vjlo = max(vlo, (int)ceilf((float)(j - 1) / sw) - 1), vjhi = min(vhi, (int)floorf((float)(j + 1) / sw) + 1);
-  float4 a = z4;
-  for (int v = vjlo; v <= vjhi; ++v) {
-    const int q = v - vlo;
-    const float l = tab_l[q];
-    const float w = (tab_i0[q] == j ? 1.f - l : 0.f) + (tab_i1[q] == j ? l : 0.f);
-    const float4 gq = t[q][tid & (UPB_CT - 1)];
-    a.x = __builtin_fmaf(w, gq.x, a.x); a.y = __builtin_fmaf(w, gq.y, a.y);
-    a.z = __builtin_fmaf(w, gq.z, a.z); a.w = __builtin_fmaf(w, gq.w, a.w);
+  // phase 2: upsample_bwd_tile_kernel's, one (source column, channel vector) per thread and owned row
+  const int cv = tid & (UPB_CT - 1), c4 = ct * UPB_CT + cv;
+  for (int j = j0 + (tid >> 4); j <= jlast; j += 256 / UPB_CT) {
+    const int vjlo = max(vlo, (int)ceilf((float)(j - 1) / sw) - 1), vjhi = min(vhi, (int)floorf((float)(j + 1) / sw) + 1);
+    float4 a[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) a[r] = z4;
+    for (int v = vjlo; v <= vjhi; ++v) {
+      const int qi = v - vlo;
+      const float l = tab_l[qi];
+      const float w = (tab_i0[qi] == j ? 1.f - l : 0.f) + (tab_i1[qi] == j ? l : 0.f);
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        const float4 gq = t[r][qi][cv];
+        a[r].x = __builtin_fmaf(w, gq.x, a[r].x); a[r].y = __builtin_fmaf(w, gq.y, a[r].y);
+        a[r].z = __builtin_fmaf(w, gq.z, a[r].z); a[r].w = __builtin_fmaf(w, gq.w, a[r].w);
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      if (ibase + r >= Hs) break;
+      float4* o = reinterpret_cast<float4*>(dx) + (((size_t)n * Hs + ibase + r) * Ws + j) * C4 + c4;
+      float4 s = a[r];
+      if (accum) {
+        const float4 b = *o;
+        s.x += b.x; s.y += b.y; s.z += b.z; s.w += b.w;
+      }
+      *o = s;
+    }
   }
-  float4* o = reinterpret_cast<float4*>(dx) + (((size_t)n * Hs + i) * Ws + j) * C4 + c4;
-  if (accum) {
-    const float4 b = *o;
-    a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w;
-  }
-  *o = a;
 }
 
+// destination-column window of J source columns (upsample_bwd_tile_kernel's host check)
+static int upb_vspan(int J, float sw) { return (int)floorf((float)(J + 1) / sw) + 4; }
+
+template <typename T, int NCH, int WA, int R, int J, int RB, int OCC>
+static void launch_upb_pw_tile(hipStream_t st, int N, int C, int Hs, int Ws, int up_h, int up_w, int pt, int pl, int Hp,
+                               int Wp, float sh, float sw, const float* d_up, const void* dgw, const void* wt, float* dx,
+                               int accum) {
+  const int ntj = cdiv(Ws, J), ntc = C / 64;
+  const unsigned nblk = (unsigned)((long long)N * cdiv(Hs, R) * ntj * ntc);
+  hipLaunchKernelGGL((upsample_bwd_pw_kernel<T, NCH, WA, R, J, RB, OCC>), dim3(nblk), dim3(256), 0, st, N, C, Hs, Ws,
+                     up_h, up_w, pt, pl, Hp, Wp, sh, sw, d_up, (const uint4*)dgw, (const uint4*)wt, dx, accum, ntj, ntc);
+}
+
+// The tile per chunk count NCH = Ci / 32, by measurement at the bench's four gate levels (4 images, bf16; us per call
+// back to back, against the one-row tile this kernel replaced):
+//   NCH 1 (C 64, 512^2)    2 tiles per wave, 2 rows, 24 columns, 2 rows per stage      142.4 -> 103.5
+//   NCH 2 (C 128, 256^2)   4 tiles per wave, 4 rows, 24 columns, 1 row per stage        88.9 ->  58.5
+//   NCH 4 (C 256, 128^2)   the same                                                     96.8 ->  42.0
+//   NCH 8 (C 512, 64^2)    2 tiles per wave, 4 rows, 16 columns, 1 row per stage        81.4 ->  36.3
+// With 4 tiles per wave a wave forms all 64 channels of its pixels and dgw is loaded by one wave, not by four: from
+// NCH 2 on dgw is most of what a block loads.  24 source columns are 52 window columns, four 16-column groups for four
+// waves (16 columns: 36, three groups).  4 rows hold 61 KB of LDS (two blocks per CU), which the 512^2 level does not
+// repay.  Where the window of 24 columns does not fit the LDS tile (narrow maps) the same form runs on 16.
 template <typename T>
-static void launch_upb_pw(int nch, unsigned nblk, hipStream_t st, int N, int C, int Hs, int Ws, int up_h, int up_w,
-                          int pt, int pl, int Hp, int Wp, float sh, float sw, const float* d_up, const void* dgw,
-                          const void* wt, float* dx, int accum, int ntj, int ntc) {
-  const uint4* x = (const uint4*)dgw;
-  const uint4* w = (const uint4*)wt;
-  // 16-channel tiles per wave: 2 where the weight fragments leave room (a wave then reads whole 128-byte lines of
-  // d_up and dgw is loaded by two waves, not four: 122.6 -> 102.2 us at 4 x 256^2, C 128; 143.1 -> 141.4 us at
-  // 4 x 512^2, C 64).  UNET_GUP_WA: A/B override, read per call
-  const char* e = getenv("UNET_GUP_WA");
-  const int wa = e ? atoi(e) : 2;
-#define UPB_PW_LAUNCH_WA(NCH, WA)                                                                                      \
-  hipLaunchKernelGGL((upsample_bwd_pw_kernel<T, NCH, WA>), dim3(nblk), dim3(256), 0, st, N, C, Hs, Ws, up_h, up_w, pt, \
-                     pl, Hp, Wp, sh, sw, d_up, x, w, dx, accum, ntj, ntc)
-#define UPB_PW_LAUNCH(NCH)                   \
-  do {                                       \
-    if (wa == 2) UPB_PW_LAUNCH_WA(NCH, 2);   \
-    else UPB_PW_LAUNCH_WA(NCH, 1);           \
-  } while (0)
-  if (nch == 1) UPB_PW_LAUNCH(1);
-  else if (nch == 2) UPB_PW_LAUNCH(2);
-  else if (nch == 4) UPB_PW_LAUNCH_WA(4, 1);   // (two tiles per wave spill with 4 or 8 weight fragments each)
-  else UPB_PW_LAUNCH_WA(8, 1);
-#undef UPB_PW_LAUNCH
-#undef UPB_PW_LAUNCH_WA
+static void launch_upb_pw(int nch, hipStream_t st, int N, int C, int Hs, int Ws, int up_h, int up_w, int pt, int pl,
+                          int Hp, int Wp, float sh, float sw, const float* d_up, const void* dgw, const void* wt,
+                          float* dx, int accum) {
+#define UPB_ARGS st, N, C, Hs, Ws, up_h, up_w, pt, pl, Hp, Wp, sh, sw, d_up, dgw, wt, dx, accum
+  const bool j24 = upb_vspan(24, sw) <= UPB_VMAX;
+  if (nch == 1) {
+    if (j24) launch_upb_pw_tile<T, 1, 2, 2, 24, 2, 4>(UPB_ARGS);
+    else launch_upb_pw_tile<T, 1, 2, 2, 16, 2, 4>(UPB_ARGS);
+  } else if (nch == 2) {
+    if (j24) launch_upb_pw_tile<T, 2, 4, 4, 24, 1, 2>(UPB_ARGS);
+    else launch_upb_pw_tile<T, 2, 4, 4, 16, 1, 2>(UPB_ARGS);
+  } else if (nch == 4) {
+    if (j24) launch_upb_pw_tile<T, 4, 4, 4, 24, 1, 2>(UPB_ARGS);
+    else launch_upb_pw_tile<T, 4, 4, 4, 16, 1, 2>(UPB_ARGS);
+  } else {
+    launch_upb_pw_tile<T, 8, 2, 4, 16, 1, 2>(UPB_ARGS);
+  }
+#undef UPB_ARGS
 }
 
 // NHWC gather adjoint: dx[n,i,j,c] (+)= Σ_{u,v} wy(u,i) wx(v,j) d_up[n, u+pt, v+pl, c]
@@ -1287,14 +1326,18 @@ int unet_upsample_bwd(long long N, int C, int Hs, int Ws, int up_h, int up_w, in
 }
 
 // geometry upsample_bwd_pw_kernel serves: the 16-bit operand types, whole 64-channel tiles, 1 / 2 / 4 / 8 chunks of
-// 32 projection channels (the weight fragments are a register array), and exactly the geometry on which
-// unet_upsample_bwd launches upsample_bwd_tile_kernel (the fused result is defined as that kernel's)
+// 32 projection channels (the weight fragments are a register array), and the geometry on which unet_upsample_bwd
+// launches upsample_bwd_tile_kernel (the fused result is defined as that kernel's chain).  A window is at most the
+// whole map, so a map of up to 8 rows or columns is served whatever its scale (a 2-row source: scale 1/3, whose
+// window bound rounds to 9); unet_upsample_bwd runs such a map on another kernel, and a caller that needs the bits
+// of the two launches (AttentionGate.up_fused_ok) leaves those maps out.  The kernel's row table holds 64
+// destination rows per row group: 19 at most at the scales admitted here
 int unet_upsample_bwd_pw_ok(int dtype, long long N, int C, int Hs, int Ws, int up_h, int up_w, int pad_t, int pad_l,
                             int Hp, int Wp, float sh, float sw, int Ci) {
   if (dtype != UNET_BF16 && dtype != UNET_F16) return 0;
   if (N < 1 || C < 64 || C % 64 || (Ci != 32 && Ci != 64 && Ci != 128 && Ci != 256)) return 0;
   if (Hs < 1 || Ws < 1 || up_h < 1 || up_w < 1 || Hp < 1 || Wp < 1) return 0;
-  auto span = [](float sc, int up) { return sc > 0.f ? (int)floorf(2.f / sc) + 3 : up + 8; };
+  auto span = [](float sc, int up) { return sc > 0.f ? min(up, (int)floorf(2.f / sc) + 3) : up + 8; };
   if (span(sh, up_h) > 8 || span(sw, up_w) > 8) return 0;
   const int vspan = (int)floorf((float)(UPB_J + 1) / sw) + 4;
   const char* e = getenv("UNET_UPB_TILE");
@@ -1312,14 +1355,12 @@ int unet_upsample_bwd_pw(int dtype, long long N, int C, int Hs, int Ws, int up_h
     set_error("unet_upsample_bwd_pw: geometry not served (unet_upsample_bwd_pw_ok)");
     return -1;
   }
-  const int ntj = cdiv(Ws, UPB_J), ntc = C / 64;
-  const unsigned nblk = (unsigned)(N * Hs * ntj * ntc);
   if (dtype == UNET_F16)
-    launch_upb_pw<f16>(Ci / 32, nblk, (hipStream_t)stream, (int)N, C, Hs, Ws, up_h, up_w, pad_t, pad_l, Hp, Wp, sh, sw,
-                       d_up, dgw, wt_packed, dx, accum, ntj, ntc);
+    launch_upb_pw<f16>(Ci / 32, (hipStream_t)stream, (int)N, C, Hs, Ws, up_h, up_w, pad_t, pad_l, Hp, Wp, sh, sw, d_up, dgw,
+                       wt_packed, dx, accum);
   else
-    launch_upb_pw<bf16>(Ci / 32, nblk, (hipStream_t)stream, (int)N, C, Hs, Ws, up_h, up_w, pad_t, pad_l, Hp, Wp, sh, sw,
-                        d_up, dgw, wt_packed, dx, accum, ntj, ntc);
+    launch_upb_pw<bf16>(Ci / 32, (hipStream_t)stream, (int)N, C, Hs, Ws, up_h, up_w, pad_t, pad_l, Hp, Wp, sh, sw, d_up, dgw,
+                        wt_packed, dx, accum);
   return check_launch("upsample_bwd_pw");
 }
 

@@ -487,13 +487,15 @@ class GateStage:
         two-launch path would run."""
         if prec.code not in (L.BF16, L.F16) or os.environ.get("UNET_NO_GUP_FUSE"):   # (env: A/B switch)
             return False
-        # per-level policy, measured at the bench size (bs 4, bf16; W_g dgrad + adjoint -> fused, us per step,
-        # profiles/r07_layerprof_gup_{off,on,deep}.txt):
-        #   Ci 32 (512^2) 173.7 -> 139.9    Ci 64 (256^2) 116.1 -> 99.5    Ci 128 (128^2) 65.2 -> 100.5    Ci 256 (64^2) 40.2 -> 86.7
-        # with 4 or 8 chunks of projection channels every wave of every 64-channel tile streams the window's dgw
-        # again (from L2) and the deep maps lose: the kernel serves them (unet_upsample_bwd_pw_ok) but they keep the
-        # two launches.  UNET_GUP_DEEP=1 fuses them too (to re-measure)
-        if self.ci > 64 and not os.environ.get("UNET_GUP_DEEP"):
+        # every level fuses: measured at the bench size (bs 4, bf16; us per step, the one-row fused tile at Ci <= 64
+        # and W_g dgrad + adjoint below it -> the row-group tile; layer profiles of both trees on one box,
+        # profiles/r08_layerprof_gup_rows_{parent,tree}.txt):
+        #   Ci 32 (512^2) 138.3 -> 98.3      Ci 64 (256^2) 97.4 -> 61.8
+        #   Ci 128 (128^2) 44.6 + 20.9 = 65.5 -> 44.1      Ci 256 (64^2) 26.9 + 13.1 = 40.0 -> 37.1
+        # four levels 341.2 -> 241.3; the 64^2 level gains least (its two launches measured 39.6 in a second profile)
+        # a map of up to 8 rows or columns: the kernel serves it, but the two-launch adjoint is then not the tiled
+        # kernel whose bits the fused call has
+        if min(x.H, x.W) <= 8:
             return False
         d = L.ConvDesc()
         d.dtype, d.N, d.H, d.W, d.Cin, d.Cout, d.ksize, d.nsrc = prec.code, x.N, x.H, x.W, self.ci, g.C, 1, 1
