@@ -29,7 +29,7 @@ extern "C" {
 /* unet_version() of a library built from this header.  110: unet_conv_desc gained `workspace` (round 5);
  * a caller built against an older header must not pass its (shorter) descriptors to this library.
  * 111: unet_aug_params, unet_aug_elastic_field and unet_aug_apply added (no existing layout changed) */
-#define UNET_ABI_VERSION 112
+#define UNET_ABI_VERSION 113
 
 enum { UNET_F32 = 0, UNET_BF16 = 1, UNET_F16 = 2 };  /* operand (activation / weight) type */
 enum { UNET_ERR_ARG = 1001, UNET_ERR_UNSUPPORTED = 1002 };
@@ -232,6 +232,24 @@ int unet_bn_bwd_reduce_pool(int dtype, long long N, int H, int W, int C, const f
 int unet_bn_bwd_apply_pool(int dtype, long long N, int H, int W, int C, const float* da, const float* g2,
                            const uint8_t* code, int ph, int pw, const void* y, const float* scale, const float* shift,
                            int relu, const float* coef, void* dy, void* stream);
+/* The two pooled passes of an attention Up block's skip activation, with `da` formed on the fly from the
+ * operands of the gate's W_x input gradient (unet_conv, UNET_OUT_F32_GATED, accum 0) instead of read back:
+ *   da = W_x^T dxw + sigmoid(gate_ab[0] * gate_p + gate_ab[1]) * dxs
+ * dxs fp32 [P][C], dxw 16-bit [P][Ci], wt_packed = unet_pack_weight(W_x, transpose = 1).  partial, dgamma, dbeta,
+ * coef and dy have the bits of that dgrad followed by unet_bn_bwd_reduce_pool / _apply_pool.  _ok: whether the
+ * shape is served (16-bit operands, C 64 / 128, Ci 32 / 64); the caller also checks that the three-launch dgrad
+ * would run on the 1x1 MFMA kernel (unet_conv_variant), whose bits these are.                     */
+int unet_bn_bwd_pool_gate_ok(int dtype, long long N, int H, int W, int C, int Ci);
+int unet_bn_bwd_reduce_pool_gate(int dtype, long long N, int H, int W, int C, int Ci, const float* dxs,
+                                 const void* dxw, const void* wt_packed, const float* gate_p, const float* gate_ab,
+                                 const float* g2, const uint8_t* code, int ph, int pw, const void* y,
+                                 const float* scale, const float* shift, int relu, const float* mean,
+                                 const float* invstd, float* partial, void* stream);
+int unet_bn_bwd_apply_pool_gate(int dtype, long long N, int H, int W, int C, int Ci, const float* dxs,
+                                const void* dxw, const void* wt_packed, const float* gate_p, const float* gate_ab,
+                                const float* g2, const uint8_t* code, int ph, int pw, const void* y,
+                                const float* scale, const float* shift, int relu, const float* coef, void* dy,
+                                void* stream);
 
 /* ---- attention gate (AttentionGate.forward/backward) — layers.py:171-192 ---------------------- */
 /* p = sum_c wpsi_c * relu(sg*gw+bg + sx*xw+bx) ; partial sums of p                               */

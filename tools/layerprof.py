@@ -50,6 +50,13 @@ def _call(name, *args):
         _, N, C, Hs, Ws, _, _, _, _, Hp, Wp = args[:11]
         Ci, accum = args[15], args[18]
         hb = (name, N * Hp * Wp * (4 * C + 2 * Ci) + N * Hs * Ws * C * 4 * (1 + accum))
+    if name in ("unet_bn_bwd_reduce_pool_gate", "unet_bn_bwd_apply_pool_gate"):
+        # the pooled BN-backward passes that form the gate's skip gradient on the fly (not in the bench line's hbm
+        # block): d(x*s), dxw, p, y, the pooled gradient and its codes read once; the apply writes dy
+        dt, N, H, W, C, Ci, ph, pw = args[0], args[1], args[2], args[3], args[4], args[5], args[13], args[14]
+        P, es = N * H * W, (4 if dt == 0 else 2)
+        hb = (name, P * (4 * C + 2 * Ci + 4 + es * C) + N * ph * pw * C * 5
+              + (P * C * es if name.startswith("unet_bn_bwd_apply") else 0))
     if hb is not None and name not in ("unet_conv", "unet_conv_wgrad"):
         info = f"{name} {hb[1] / 1e6:.1f} MB"
         fl = -hb[1]          # negative: algorithmic bytes (HBM-bound line)

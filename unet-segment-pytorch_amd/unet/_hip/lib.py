@@ -100,6 +100,12 @@ _SIGS = {
                                         c_vp, c_int, c_vp, c_vp, c_vp, c_vp]),
     "unet_bn_bwd_apply_pool": (c_int, [c_int, c_ll, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_int, c_int, c_vp, c_vp,
                                        c_vp, c_int, c_vp, c_vp, c_vp]),
+    "unet_bn_bwd_pool_gate_ok": (c_int, [c_int, c_ll, c_int, c_int, c_int, c_int]),
+    "unet_bn_bwd_reduce_pool_gate": (c_int, [c_int, c_ll, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                             c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_vp,
+                                             c_vp]),
+    "unet_bn_bwd_apply_pool_gate": (c_int, [c_int, c_ll, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                            c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_vp]),
     "unet_colsum": (c_int, [c_vp, c_int, c_int, c_vp, c_int, c_vp]),
     "unet_bn_finalize_multi": (c_int, [c_int, ctypes.POINTER(BnFinJob), c_vp]),
     "unet_bn_bwd_finalize_multi": (c_int, [c_int, ctypes.POINTER(BnBwdFinJob), c_vp]),
@@ -164,7 +170,7 @@ _SIGS = {
 }
 
 _lib = None
-ABI_VERSION = 112  # include/unet_hip.h UNET_ABI_VERSION
+ABI_VERSION = 113  # include/unet_hip.h UNET_ABI_VERSION
 
 # UNET_GUARD=1: bounds-checking debug mode (csrc/guard_alloc.cpp).  Every device allocation of the process
 # gets guard bands and every library call is bracketed by a device sync + a check of all bands, so an
@@ -176,7 +182,7 @@ _guard = None
 _NO_LAUNCH = {"unet_last_error", "unet_version", "unet_conv_mtiles", "unet_conv_stats_rows", "unet_conv_variant",
               "unet_wgrad_variant", "unet_conv_act_out_ok", "unet_conv_workspace", "unet_packed_weight_elems", "unet_wgrad_workspace",
               "unet_bn_bwd_reduce_rows", "unet_gate_psi_rows", "unet_gate_bwd2_rows", "unet_convt_bwd_rows",
-              "unet_outconv_rows", "unet_loss_rows", "unet_upsample_bwd_pw_ok"}
+              "unet_outconv_rows", "unet_loss_rows", "unet_upsample_bwd_pw_ok", "unet_bn_bwd_pool_gate_ok"}
 
 
 class HipLibraryError(RuntimeError):

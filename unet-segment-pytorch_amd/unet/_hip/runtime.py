@@ -188,7 +188,7 @@ class Act:
     for a single-consumer activation in bf16 mode (`grad_single`)."""
 
     __slots__ = ("data", "N", "H", "W", "C", "ab", "relu", "mean", "invstd", "grad", "_grad_init", "keep",
-                 "bn_owned", "pool_grad", "batch_stats", "oc_fused", "fin_job")
+                 "bn_owned", "pool_grad", "batch_stats", "oc_fused", "fin_job", "gate_fused")
 
     def __init__(self, data: torch.Tensor, ab: Optional[torch.Tensor], relu: bool,
                  mean: Optional[torch.Tensor] = None, invstd: Optional[torch.Tensor] = None):
@@ -211,6 +211,10 @@ class Act:
         self.oc_fused = None
         # set by ConvBN.forward(defer_fin=True): (unet_bn_finalize_job, its partial sums) until finalize_many runs it
         self.fin_job = None
+        # set by GateStage.backward when the gate's gradient of this skip activation is deferred: (materialise,
+        # d_xs, dxw, p, psi_ab, packed W_x^T, ...) — the pooled BN backward forms W_x^T dxw + s * d(x s) on the fly
+        # (unet_bn_bwd_*_pool_gate); any other use of the gradient first stores it (flush_gate)
+        self.gate_fused = None
 
     @property
     def scale(self):
@@ -225,8 +229,17 @@ class Act:
         return self.N * self.H * self.W
 
     # -- gradient buffer management --
+    def flush_gate(self) -> None:
+        """Store a deferred gate gradient (gate_fused) with the launch that was deferred: it becomes the first
+        contribution to `grad`, as it was without the deferral."""
+        gf = self.gate_fused
+        if gf is not None:
+            self.gate_fused = None
+            gf[0](self, *gf[1:])
+
     def grad_target(self):
         """(buffer, accumulate) for the next contribution to this activation's gradient."""
+        self.flush_gate()
         if self.grad is None:
             self.grad = f32(self.N, self.H, self.W, self.C, device=self.data.device)
         acc = self._grad_init
@@ -236,12 +249,14 @@ class Act:
     def grad_single(self, dtype: torch.dtype) -> torch.Tensor:
         """Buffer for the one and only contribution to this activation's gradient (stored, not
         accumulated): a DoubleConv's middle activation, whose only consumer is the second conv."""
-        assert self.grad is None and not self._grad_init, "activation has another gradient contribution"
+        assert self.grad is None and not self._grad_init and self.gate_fused is None, \
+            "activation has another gradient contribution"
         self.grad = torch.empty(self.N, self.H, self.W, self.C, dtype=dtype, device=self.data.device)
         self._grad_init = True
         return self.grad
 
     def grad_zeroed(self) -> torch.Tensor:
+        self.flush_gate()
         if self.grad is None:
             self.grad = f32(self.N, self.H, self.W, self.C, device=self.data.device)
         if not self._grad_init:
@@ -250,6 +265,7 @@ class Act:
         return self.grad
 
     def has_grad(self) -> bool:
+        self.flush_gate()   # (a deferred gate gradient is a gradient: whoever asks gets it stored)
         return self._grad_init
 
     # -- source descriptors --

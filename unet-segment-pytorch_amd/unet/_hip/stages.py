@@ -169,6 +169,14 @@ class ConvBN:
         pool = a.pool_grad
         if a.oc_fused is not None:
             return self._bn_backward_oc(prec, a, grads)
+        gate = None
+        if a.gate_fused is not None:
+            # the gate's deferred gradient is the only other contribution and a pooled gradient is folded in: both
+            # passes form it on the fly; otherwise it is stored first, by the launch that was deferred
+            if pool is not None and fused is None and not os.environ.get("UNET_NO_GATE_BN_FUSE"):
+                gate, a.gate_fused = a.gate_fused, None
+            else:
+                a.flush_gate()
         assert a.has_grad() or pool is not None, "activation gradient missing"
         gcode = {torch.bfloat16: L.BF16, torch.float16: L.F16}.get(a.grad.dtype, L.F32) if a.has_grad() else L.F32
         if pool is not None:
@@ -179,8 +187,16 @@ class ConvBN:
             da = vp(a.grad) if a.has_grad() else None
             rows = L.load().unet_bn_bwd_reduce_rows(P, C)
             part = f32(2, rows, C, device=dev)
-            L.call("unet_bn_bwd_reduce_pool", prec.code, a.N, a.H, a.W, C, da, vp(g2), vp(code), ph, pw,
-                   vp(a.data), vp(a.ab[0]), vp(a.ab[1]), int(a.relu), vp(a.mean), vp(a.invstd), vp(part), stream())
+            if gate is not None:
+                assert not a.has_grad()
+                _, d_xs, dxw, gp, gab, wt = gate[:6]
+                gargs = (prec.code, a.N, a.H, a.W, C, dxw.shape[-1], vp(d_xs), vp(dxw), vp(wt), vp(gp), vp(gab),
+                         vp(g2), vp(code), ph, pw, vp(a.data), vp(a.ab[0]), vp(a.ab[1]), int(a.relu))
+                L.call("unet_bn_bwd_reduce_pool_gate", *gargs, vp(a.mean), vp(a.invstd), vp(part), stream())
+            else:
+                L.call("unet_bn_bwd_reduce_pool", prec.code, a.N, a.H, a.W, C, da, vp(g2), vp(code), ph, pw,
+                       vp(a.data), vp(a.ab[0]), vp(a.ab[1]), int(a.relu), vp(a.mean), vp(a.invstd), vp(part),
+                       stream())
         elif fused is not None:
             part, rows = fused
         else:
@@ -194,7 +210,10 @@ class ConvBN:
         grads.put(self.bn.weight, dgamma)
         grads.put(self.bn.bias, dbeta)
         dy = torch.empty(a.N, a.H, a.W, C, dtype=prec.torch_dtype, device=dev)
-        if pool is not None:
+        if gate is not None:
+            L.call("unet_bn_bwd_apply_pool_gate", *gargs, vp(coef), vp(dy), stream())
+            a.pool_grad = None
+        elif pool is not None:
             L.call("unet_bn_bwd_apply_pool", prec.code, a.N, a.H, a.W, C, da, vp(g2), vp(code), ph, pw, vp(a.data),
                    vp(a.ab[0]), vp(a.ab[1]), int(a.relu), vp(coef), vp(dy), stream())
             a.pool_grad = None
@@ -250,6 +269,12 @@ class ConvBN:
             return
         wt = self.pre_wt if self.pre_wt is not None else pack_weight(self.conv.weight, prec, transpose=True)
         self.pre_wt = None
+        self.dgrad_launch(prec, dy, wt, dgrad)
+
+    def dgrad_launch(self, prec: Precision, dy: torch.Tensor, wt: torch.Tensor, dgrad: dict):
+        """The input-gradient launch of conv_backward (wt: the packed transposed weight)."""
+        N, H, W, cout = dy.shape
+        dev = dy.device
         d = _conv_desc(prec, N, H, W, self.cout, self.cin, self.k, [_plain_src(dy)], wt)
         ws = None   # split-K scratch (L.attach_workspace), attached once every other field is set
         if dgrad["mode"] == "y":
@@ -332,6 +357,27 @@ class DoubleConvStage:
 
 
 # ------------------------------------------------------------------------------------------------
+# Which levels leave the gate's skip gradient to the pooled BatchNorm backward: skip channels -> smallest map
+# (pixels) that takes the route.  Measured at the bench size (bs 4, bf16; us per launch, gated W_x dgrad + pooled
+# reduce + pooled apply -> the two _pool_gate passes; layer profiles of parent and tree on one box,
+# profiles/r09_gate_bn_{parent,tree}_layerprof.txt):
+#   C 64, Ci 32 (512^2)   108.4 + 116.0 + 106.6 = 331.0 -> 115.0 + 128.2 = 243.2
+#   C 128, Ci 64 (256^2)   68.6 +  61.2 +  52.8 = 182.6 ->  67.4 +  75.1 = 142.5
+# The 128^2 and 64^2 levels (C 256 / 512) are not served: their R = 8 / 4 partial-sum chains per channel do not
+# map onto 16-pixel MFMA tiles (csrc/bn_gate.hip).  Below the pixel bound a level keeps its three launches: the
+# route is measured at the bench maps only, and the equivalence tests of the gated dgrad
+# (tests/test_gpu_fusion_equivalence.py) watch its launch at 2 x 128^2 and 2 x 98^2.
+GATE_BN_FUSE_LEVELS = {64: 65536, 128: 16384}
+
+
+def _store_gate_grad(x: Act, d_xs, dxw, gate_p, gate_ab, wt, cx, prec) -> None:
+    """Act.flush_gate's worker: the f32_gated W_x dgrad that GateStage.backward deferred, as the first
+    contribution to x.grad."""
+    dx, acc = x.grad_target()
+    cx.dgrad_launch(prec, dxw, wt, {"mode": "f32_gated", "out": dx, "accum": acc, "dxs": d_xs, "gate_p": gate_p,
+                                    "gate_ab": gate_ab})
+
+
 class GateStage:
     """AttentionGate — layers.py:126-192: W_g(g_up), W_x(x) (1x1 conv + BN), relu(sum), psi
     (1x1 conv -> BN(1) -> sigmoid), x * psi.  g_up = bilinear(g, size=x) (:183)."""
@@ -471,6 +517,15 @@ class GateStage:
         else:
             self.cg.conv_backward(prec, dgw, self.gw_src, grads,
                                   {"mode": "f32", "out": d_gup, "accum": d_gup_accum})
+        if fuse and self._bn_fused_ok(prec, x):
+            # dx is not stored: the pooled BN backward of x forms it from these operands (unet_bn_bwd_*_pool_gate);
+            # whatever else touches x's gradient first stores it with the launch deferred here (Act.flush_gate)
+            wt_x = self.cx.pre_wt if self.cx.pre_wt is not None else pack_weight(self.cx.conv.weight, prec,
+                                                                                 transpose=True)
+            self.cx.pre_wt = None
+            self.cx.conv_backward(prec, dxw, [x.src()], grads, None)
+            x.gate_fused = (_store_gate_grad, d_xs, dxw, self.p, self.psi_ab, wt_x, self.cx, prec)
+            return (dgw, wt_g) if defer_g else None
         dx2, acc2 = x.grad_target()
         if fuse:
             self.cx.conv_backward(prec, dxw, [x.src()], grads, {"mode": "f32_gated", "out": dx2, "accum": acc2,
@@ -507,6 +562,21 @@ class GateStage:
             return False
         return bool(L.load().unet_upsample_bwd_pw_ok(prec.code, g.N, g.C, g.H, g.W, x.H, x.W, 0, 0, x.H, x.W,
                                                      up_scale(g.H, x.H), up_scale(g.W, x.W), self.ci))
+
+    def _bn_fused_ok(self, prec, x: Act) -> bool:
+        """Whether the W_x input gradient + x*s term (the f32_gated dgrad, already known to run on the 1x1 MFMA
+        kernel) may be left to x's pooled BatchNorm backward: x has no gradient contribution yet and is a
+        ConvBN's output that DownStage.backward will hand a folded pooled gradient (its conditions)."""
+        if os.environ.get("UNET_NO_GATE_BN_FUSE") or os.environ.get("UNET_NO_POOL_FOLD"):   # (env: A/B switches)
+            return False
+        cv = x.C // 8
+        if not (x.bn_owned and x.ab is not None and not x.has_grad() and x.grad is None and x.pool_grad is None
+                and x.oc_fused is None and x.gate_fused is None and x.C % 8 == 0 and cv <= 256
+                and cv & (cv - 1) == 0 and x.pixels < 2 ** 31):
+            return False
+        if x.pixels < GATE_BN_FUSE_LEVELS.get(x.C, 2 ** 31):
+            return False
+        return bool(L.load().unet_bn_bwd_pool_gate_ok(prec.code, x.N, x.H, x.W, x.C, self.ci))
 
     def _wx_gated_ok(self, prec, x: Act) -> bool:
         """Whether the W_x dgrad (Ci -> Cx 1x1) runs on the kernel that serves UNET_OUT_F32_GATED."""
