@@ -17,7 +17,7 @@ from torch.autograd.function import once_differentiable
 from . import lib as L
 from .runtime import (Act, act_from_nchw, act_to_nchw, f32, get_precision, grad_nchw_to_nhwc, grad_nhwc_to_nchw,
                       nchw_src, require_device, stream, up_scale, vp)
-from .stages import (DoubleConvStage, DownStage, GateStage, Grads, NetworkPlan, OutConvStage, UpStage,
+from .stages import (DgradF32, DoubleConvStage, DownStage, GateStage, Grads, NetworkPlan, OutConvStage, UpStage,
                      mark_tracked)
 
 
@@ -212,7 +212,7 @@ class _ModulePlan:
             if self.needs[0]:
                 N, C, H, W = x.shape
                 gx = f32(N, H, W, C, device=x.device)
-                self.st.backward(prec, grads, {"mode": "f32", "out": gx, "accum": 0})
+                self.st.backward(prec, grads, DgradF32(gx))
                 return [grad_nhwc_to_nchw(gx)]
             self.st.backward(prec, grads, None)
             return [None]

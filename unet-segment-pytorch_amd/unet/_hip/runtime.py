@@ -5,7 +5,7 @@ from __future__ import annotations
 import ctypes
 import os
 from dataclasses import dataclass
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -137,13 +137,19 @@ def up_scale(in_size: int, out_size: int) -> float:
     return float(np.float32(in_size - 1) / np.float32(out_size - 1))
 
 
-def pack_weight(w: torch.Tensor, prec: Precision, transpose: bool) -> torch.Tensor:
+def _pack_operands(w: torch.Tensor, prec: Precision, transpose: bool):
+    """One OIHW weight's pack operands: (fp32 contiguous source, empty packed destination, Cout, Cin, ksize)."""
     cout, cin, k = w.shape[0], w.shape[1], w.shape[2]
     n = L.load().unet_packed_weight_elems(prec.code, cout, cin, k, int(transpose))
     out = torch.empty(n, dtype=prec.torch_dtype, device=w.device)
     wc = w.detach()
     if wc.dtype != torch.float32 or not wc.is_contiguous():
         wc = wc.float().contiguous()
+    return wc, out, cout, cin, k
+
+
+def pack_weight(w: torch.Tensor, prec: Precision, transpose: bool) -> torch.Tensor:
+    wc, out, cout, cin, k = _pack_operands(w, prec, transpose)
     L.call("unet_pack_weight", prec.code, vp(wc), vp(out), cout, cin, k, int(transpose), stream())
     return out
 
@@ -151,15 +157,9 @@ def pack_weight(w: torch.Tensor, prec: Precision, transpose: bool) -> torch.Tens
 def pack_many(items, prec: Precision):
     """Pack several OIHW weights (list of (weight, transpose)) with one launch per 64; returns the
     packed tensors in order."""
-    lib = L.load()
     outs, jobs, keep = [], [], []
     for w, transpose in items:
-        cout, cin, k = w.shape[0], w.shape[1], w.shape[2]
-        n = lib.unet_packed_weight_elems(prec.code, cout, cin, k, int(transpose))
-        out = torch.empty(n, dtype=prec.torch_dtype, device=w.device)
-        wc = w.detach()
-        if wc.dtype != torch.float32 or not wc.is_contiguous():
-            wc = wc.float().contiguous()
+        wc, out, cout, cin, k = _pack_operands(w, prec, transpose)
         keep.append(wc)
         j = L.PackJob()
         j.w, j.packed, j.Cout, j.Cin, j.ksize, j.transpose = wc.data_ptr(), out.data_ptr(), cout, cin, k, int(transpose)
@@ -181,11 +181,49 @@ def fill_zero(t: torch.Tensor) -> None:
 # ------------------------------------------------------------------------------------------------
 
 
+class PoolGrad(NamedTuple):
+    """Act.pool_grad: a Down block's input gradient left at the pooled resolution (DownStage.backward).  The
+    BatchNorm backward that consumes the activation's gradient routes it through the 2x2 argmax codes."""
+    g2: torch.Tensor      # fp32 [N, ph, pw, C]
+    code: torch.Tensor    # uint8 argmax codes of the forward's pool, same shape
+    ph: int
+    pw: int
+
+
+class OutConvGrad(NamedTuple):
+    """Act.oc_fused: OutConv is the activation's only consumer and its gradient W^T dl is not stored
+    (OutConvStage.backward).  The BatchNorm-backward sums are already taken; the apply recomputes the gradient."""
+    dl: torch.Tensor      # fp32 NCHW logit gradient
+    w: torch.Tensor       # fp32 [K, C] OutConv weight
+    k: int
+    part: torch.Tensor    # BatchNorm-backward partial sums [2][rows][C]
+    rows: int
+
+
+class GateGrad(NamedTuple):
+    """Act.gate_fused: an attention gate's gradient of its skip activation, W_x^T dxw + s * d(x s), not yet
+    stored (GateStage.backward).  `cx.store_gate_grad` is the launch that was deferred."""
+    d_xs: torch.Tensor    # fp32 gradient of x * s
+    dxw: torch.Tensor     # op-dtype gradient at W_x's output
+    gate_p: torch.Tensor  # psi's pre-activation and BatchNorm affine (the gate s)
+    gate_ab: torch.Tensor
+    wt: torch.Tensor      # packed W_x^T
+    cx: object            # the gate's W_x ConvBN
+    prec: Precision
+
+
 class Act:
     """A stored NHWC tensor plus the per-channel affine (+ReLU) that makes it the reference's
     activation (relu(bn(y)) of a DoubleConv half, or the identity for a materialised input).
     `grad` is the NHWC gradient w.r.t. that activation, accumulated by its consumers: fp32, or bf16
-    for a single-consumer activation in bf16 mode (`grad_single`)."""
+    for a single-consumer activation in bf16 mode (`grad_single`).
+
+    Three consumers may leave their contribution unstored for the BatchNorm backward that consumes the
+    gradient (set on a ConvBN's output only, `bn_owned`): `pool_grad`, `oc_fused` and `gate_fused`.  A pending
+    `gate_fused` is a gradient like a stored one: any other contribution (`grad_target`, `grad_zeroed`) and any
+    question about the gradient (`has_grad`, `grad_single`'s assertion) first stores it with the launch that was
+    deferred (`flush_gate`), so it is the first contribution to `grad` as it was without the deferral.  Only the
+    pooled BatchNorm backward takes it unstored."""
 
     __slots__ = ("data", "N", "H", "W", "C", "ab", "relu", "mean", "invstd", "grad", "_grad_init", "keep",
                  "bn_owned", "pool_grad", "batch_stats", "oc_fused", "fin_job", "gate_fused")
@@ -201,20 +239,13 @@ class Act:
         self.grad = None
         self._grad_init = False
         self.keep = None
-        # set by ConvBN.forward: the gradient is consumed by that ConvBN's BatchNorm backward, which can
-        # fold a Down block's pooled gradient (pool_grad = (g2, code, ph, pw)) in on the fly
-        self.bn_owned = False
-        self.pool_grad = None
+        self.bn_owned = False     # set by ConvBN.forward: that ConvBN's BatchNorm backward consumes the gradient
         self.batch_stats = True   # False: an eval-mode BN (running statistics) produced it
-        # set by OutConvStage.backward when OutConv is the only consumer: (dl, w, K, bn partial sums, rows) — the
-        # gradient W^T dl is recomputed by the BN-backward apply instead of being stored
-        self.oc_fused = None
+        self.pool_grad: Optional[PoolGrad] = None
+        self.oc_fused: Optional[OutConvGrad] = None
+        self.gate_fused: Optional[GateGrad] = None
         # set by ConvBN.forward(defer_fin=True): (unet_bn_finalize_job, its partial sums) until finalize_many runs it
         self.fin_job = None
-        # set by GateStage.backward when the gate's gradient of this skip activation is deferred: (materialise,
-        # d_xs, dxw, p, psi_ab, packed W_x^T, ...) — the pooled BN backward forms W_x^T dxw + s * d(x s) on the fly
-        # (unet_bn_bwd_*_pool_gate); any other use of the gradient first stores it (flush_gate)
-        self.gate_fused = None
 
     @property
     def scale(self):
@@ -230,12 +261,11 @@ class Act:
 
     # -- gradient buffer management --
     def flush_gate(self) -> None:
-        """Store a deferred gate gradient (gate_fused) with the launch that was deferred: it becomes the first
-        contribution to `grad`, as it was without the deferral."""
+        """Store a pending gate gradient (see the class docstring)."""
         gf = self.gate_fused
         if gf is not None:
             self.gate_fused = None
-            gf[0](self, *gf[1:])
+            gf.cx.store_gate_grad(self, gf)
 
     def grad_target(self):
         """(buffer, accumulate) for the next contribution to this activation's gradient."""
@@ -265,7 +295,7 @@ class Act:
         return self.grad
 
     def has_grad(self) -> bool:
-        self.flush_gate()   # (a deferred gate gradient is a gradient: whoever asks gets it stored)
+        self.flush_gate()
         return self._grad_init
 
     # -- source descriptors --

@@ -12,25 +12,80 @@ the bilinear x2 upsample of each Up block's decoder input (`unet_materialize`).
 from __future__ import annotations
 
 import os
-from typing import Dict, List, Optional
+from typing import List, NamedTuple, Optional, Union
 
 import torch
 
 from . import lib as L
-from .runtime import (Act, Precision, conv_kernel_name, f32, pack_many, pack_weight, probe, stream, up_scale, vp,
-                      wgrad_kernel_name)
+from .runtime import (Act, GateGrad, OutConvGrad, PoolGrad, Precision, conv_kernel_name, f32, grad_nhwc_to_nchw,
+                      nchw_src, pack_many, pack_weight, probe, stream, up_scale, vp, wgrad_kernel_name)
+
+
+# ---- dgrad routes: where ConvBN.dgrad_launch puts a conv's input gradient ----------------------------------
+class DgradF32(NamedTuple):
+    """fp32, stored or accumulated; with `out2`, input channels from `split` on go there instead (the two
+    halves of an Up block's concat)."""
+    out: torch.Tensor
+    accum: int = 0
+    out2: Optional[torch.Tensor] = None
+    accum2: int = 0
+    split: Optional[int] = None   # None: every channel goes to `out`
+
+
+class DgradY(NamedTuple):
+    """Op dtype, stored; with `bnb` (the Act it is the gradient of) the epilogue also reduces that
+    activation's BatchNorm-backward sums, which dgrad_launch returns."""
+    out: torch.Tensor
+    bnb: Optional[Act] = None
+
+
+class DgradPool(NamedTuple):
+    """MaxPool2d backward: added into the (initialised) full-resolution fp32 gradient of the pool's input."""
+    out: torch.Tensor
+    pool_src: L.Src
+    code: Optional[torch.Tensor]   # the forward's argmax codes, where it recorded them
+
+
+class DgradGated(NamedTuple):
+    """The attention gate's W_x input gradient plus the x*s term: out (+)= s * d(x*s) + W_x^T dy, fp32."""
+    out: torch.Tensor
+    accum: int
+    dxs: torch.Tensor
+    gate_p: torch.Tensor
+    gate_ab: torch.Tensor
+
+
+Dgrad = Union[DgradF32, DgradY, DgradPool, DgradGated]
 
 
 def _conv_desc(prec: Precision, N: int, H: int, W: int, cin: int, cout: int, k: int, srcs: List[L.Src],
-               weight: torch.Tensor) -> L.ConvDesc:
+               weight: Optional[torch.Tensor]) -> L.ConvDesc:
     d = L.ConvDesc()
     d.dtype = prec.code
     d.N, d.H, d.W, d.Cin, d.Cout, d.ksize = N, H, W, cin, cout, k
     d.nsrc = len(srcs)
     for i, s in enumerate(srcs):
         d.src[i] = s
-    d.weight = weight.data_ptr()
+    d.weight = vp(weight)
     return d
+
+
+def _pw_kernel_serves(prec: Precision, x: Act, cin: int, cout: int, out_mode: int, accum: int) -> bool:
+    """Whether unet_conv runs a cin -> cout 1x1 dgrad over x's pixels, in this output mode, on the 1x1 MFMA
+    kernel (the only one with the OUT_F32_GATED epilogue, and the one whose bits the fused adjoint has)."""
+    s = L.Src()
+    s.kind, s.C, s.H, s.W = L.SRC_PLAIN, cin, x.H, x.W
+    d = _conv_desc(prec, x.N, x.H, x.W, cin, cout, 1, [s], None)
+    d.out_mode, d.split, d.accum = out_mode, cout, accum
+    return conv_kernel_name(d).startswith("pw_conv_kernel")
+
+
+def _chan_vec_ok(C: int, vec: int) -> bool:
+    """The channel constraint of the vectorised BatchNorm-backward, pool and OutConv kernels (bn_vec_ok in
+    csrc/bn.hip, unet_materialize_pool): a thread owns `vec` channels of a pixel, and the C / vec threads of a
+    pixel are a power of two of at most 256, so a thread's channels stay fixed along its grid stride."""
+    cv = C // vec
+    return C % vec == 0 and cv <= 256 and cv & (cv - 1) == 0
 
 
 def _materialize(prec: Precision, src: L.Src, N: int, H: int, W: int) -> torch.Tensor:
@@ -38,6 +93,30 @@ def _materialize(prec: Precision, src: L.Src, N: int, H: int, W: int) -> torch.T
     out = torch.empty(N, H, W, src.C, dtype=prec.torch_dtype, device="cuda")
     L.call("unet_materialize", prec.code, src, N, H, W, vp(out), stream())
     return out
+
+
+def _bn_forward_stats(bn, training: bool, use_batch: bool, stats, rows: int, C: int, count: int, mean, invstd, ab,
+                      defer: bool = False):
+    """A BatchNorm forward's per-channel epilogue: mean / invstd and the affine `ab` from the conv's partial
+    sums `stats` (batch statistics, which also update the running ones in training), or from the running
+    statistics.  defer: the batch-statistics finalize is not launched but returned as (unet_bn_finalize_job,
+    stats) for `finalize_many`; the job holds raw pointers, so the partial sums travel with it."""
+    if not use_batch:
+        # eval mode: mean / invstd are the running ones, which the backward of an eval-mode forward treats
+        # as constants (unet_bn_bwd_finalize with count 0)
+        L.call("unet_bn_eval_affine", C, vp(bn.weight), vp(bn.bias), vp(bn.running_mean), vp(bn.running_var),
+               float(bn.eps), vp(ab[0]), vp(ab[1]), vp(mean), vp(invstd), stream())
+        return None
+    upd = training and bn.track_running_stats
+    # a job has exactly the arguments of one unet_bn_finalize call, in order (include/unet_hip.h)
+    args = (vp(stats), rows, C, count, vp(bn.weight), vp(bn.bias),
+            vp(bn.running_mean) if upd else None, vp(bn.running_var) if upd else None,
+            vp(bn.num_batches_tracked) if upd else None, -1.0 if bn.momentum is None else float(bn.momentum),
+            float(bn.eps), vp(mean), vp(invstd), vp(ab[0]), vp(ab[1]))
+    if defer:
+        return L.BnFinJob(*args), stats
+    L.call("unet_bn_finalize", *args, stream())
+    return None
 
 
 def finalize_many(acts) -> None:
@@ -58,6 +137,37 @@ def _bwd_fin_job(sum_g, sum_gx, rows, C, count, gamma, mean, invstd, dgamma, dbe
     j.gamma, j.mean, j.invstd = vp(gamma), vp(mean), vp(invstd)
     j.dgamma, j.dbeta, j.accum, j.coef = vp(dgamma), vp(dbeta), 0, vp(coef)
     return j
+
+
+def _bn_backward_finalize(bn, grads: "Grads", sum_g, sum_gx, rows: int, C: int, count: int, mean,
+                          invstd) -> torch.Tensor:
+    """A BatchNorm backward's per-channel step: gamma's and beta's gradients into `grads` and the returned
+    coef[3][C] of the apply (dy = A*g + B*y + Cc), from the partial sums.  count 0: running statistics."""
+    dev = sum_g.device
+    dgamma, dbeta, coef = f32(C, device=dev), f32(C, device=dev), f32(3, C, device=dev)
+    L.call("unet_bn_bwd_finalize", vp(sum_g), vp(sum_gx), rows, C, count, vp(bn.weight), vp(mean), vp(invstd),
+           vp(dgamma), vp(dbeta), 0, vp(coef), stream())
+    grads.put(bn.weight, dgamma)
+    grads.put(bn.bias, dbeta)
+    return coef
+
+
+def _wgrad(prec: Precision, N: int, H: int, W: int, cin: int, cout: int, k: int, srcs: List[L.Src],
+           dy: torch.Tensor, dw: torch.Tensor) -> None:
+    """The weight gradient of a cin -> cout k x k conv over `srcs` with output gradient dy, stored into dw."""
+    wd = L.WgradDesc()
+    wd.dtype = prec.code
+    wd.N, wd.H, wd.W, wd.Cin, wd.Cout, wd.ksize = N, H, W, cin, cout, k
+    wd.nsrc = len(srcs)
+    for i, s in enumerate(srcs):
+        wd.src[i] = s
+    wd.dy = dy.data_ptr()
+    wd.dw = dw.data_ptr()
+    wd.accum = 0
+    ws = torch.empty(max(L.load().unet_wgrad_workspace(wd), 16), dtype=torch.uint8, device=dy.device)
+    wd.workspace = ws.data_ptr()
+    probe.launch(lambda: wgrad_kernel_name(wd), 2.0 * N * H * W * cin * cout * k ** 2,
+                 lambda: L.call("unet_conv_wgrad", wd, stream()))
 
 
 def _plain_src(t: torch.Tensor) -> L.Src:
@@ -93,14 +203,22 @@ class ConvBN:
         self.wact = None
         self.tracked = True  # a backward will follow this forward (act_out only pays off then)
 
+    def take_weight(self, prec: Precision, transpose: bool) -> torch.Tensor:
+        """The packed forward (transpose: dgrad) weight: NetworkPlan's batched pack where it made one, which
+        serves one use, else packed now."""
+        if transpose:
+            w, self.pre_wt = self.pre_wt, None
+        else:
+            w, self.pre_wp = self.pre_wp, None
+        return w if w is not None else pack_weight(self.conv.weight, prec, transpose)
+
     # ---- forward ----
     def forward(self, prec: Precision, srcs: List[L.Src], N: int, H: int, W: int, training: bool,
                 keep=None, defer_fin: bool = False) -> Act:
         """defer_fin: the batch-statistics finalize is not launched here but left on the result as
         `a.fin_job` (an unet_bn_finalize_job) for the caller to launch with others (`finalize_many`)."""
         dev = self.conv.weight.device
-        wp = self.pre_wp if self.pre_wp is not None else pack_weight(self.conv.weight, prec, transpose=False)
-        self.pre_wp = None
+        wp = self.take_weight(prec, transpose=False)
         y = torch.empty(N, H, W, self.cout, dtype=prec.torch_dtype, device=dev)
         d = _conv_desc(prec, N, H, W, self.cin, self.cout, self.k, srcs, wp)
         d.out_mode = L.OUT_Y
@@ -121,6 +239,7 @@ class ConvBN:
         bn = self.bn
         ab = f32(2, self.cout, device=dev)
         use_batch = training or not bn.track_running_stats
+        stats, mt = None, 0
         if use_batch:
             mt = L.load().unet_conv_stats_rows(d)
             stats = f32(2, self.cout, mt, device=dev)   # [2][C][rows] (unet_conv_stats_rows)
@@ -129,160 +248,96 @@ class ConvBN:
                      lambda: L.call("unet_conv", d, stream()), d.out_mode)
         mean = f32(self.cout, device=dev)
         invstd = f32(self.cout, device=dev)
-        fin_job = None
-        if use_batch:
-            upd = training and bn.track_running_stats
-            mom = -1.0 if bn.momentum is None else float(bn.momentum)
-            if defer_fin:
-                j = L.BnFinJob()
-                j.stats, j.rows, j.C, j.count = vp(stats), mt, self.cout, N * H * W
-                j.gamma, j.beta = vp(bn.weight), vp(bn.bias)
-                j.running_mean = vp(bn.running_mean) if upd else None
-                j.running_var = vp(bn.running_var) if upd else None
-                j.num_batches_tracked = vp(bn.num_batches_tracked) if upd else None
-                j.momentum, j.eps = mom, float(bn.eps)
-                j.mean, j.invstd, j.scale, j.shift = vp(mean), vp(invstd), vp(ab[0]), vp(ab[1])
-                fin_job = (j, stats)   # the job holds raw pointers: keep the partial sums alive until it runs
-            else:
-                L.call("unet_bn_finalize", vp(stats), mt, self.cout, N * H * W, vp(bn.weight), vp(bn.bias),
-                       vp(bn.running_mean) if upd else None, vp(bn.running_var) if upd else None,
-                       vp(bn.num_batches_tracked) if upd else None, mom, float(bn.eps), vp(mean), vp(invstd),
-                       vp(ab[0]), vp(ab[1]), stream())
-        else:
-            # eval mode (running statistics): mean / invstd are the running ones, which the backward of an
-            # eval-mode forward treats as constants (unet_bn_bwd_finalize with count 0)
-            L.call("unet_bn_eval_affine", self.cout, vp(bn.weight), vp(bn.bias), vp(bn.running_mean),
-                   vp(bn.running_var), float(bn.eps), vp(ab[0]), vp(ab[1]), vp(mean), vp(invstd), stream())
         a = Act(y, ab, self.relu, mean, invstd)
+        a.fin_job = _bn_forward_stats(bn, training, use_batch, stats, mt, self.cout, N * H * W, mean, invstd, ab,
+                                      defer_fin)
         a.batch_stats = use_batch
         a.keep = keep  # keeps the source tensors alive until backward
         a.bn_owned = True
-        a.fin_job = fin_job
         return a
 
     # ---- backward ----
-    def bn_backward(self, prec: Precision, a: Act, grads: Grads, fused=None) -> torch.Tensor:
-        """BatchNorm2d(+ReLU) backward: returns dy (op dtype, NHWC) at the conv output.  `fused`: the
-        (partial sums [2][rows][C], rows) the producing dgrad's epilogue already reduced (bnb_*)."""
+    def bn_backward(self, prec: Precision, a: Act, grads: Grads, sums=None) -> torch.Tensor:
+        """BatchNorm2d(+ReLU) backward: returns dy (op dtype, NHWC) at the conv output.  `sums`: the
+        (partial sums [2][rows][C], rows) the producing dgrad's epilogue already reduced (bnb_*).
+
+        Pick the gradient's source, reduce its sums unless they are there already, finalize, apply.  A source
+        is a reduce kernel, an apply kernel and the operand list `ops` that both start with."""
         dev = a.data.device
         P, C = a.pixels, a.C
-        pool = a.pool_grad
+        geo = (prec.code, a.N, a.H, a.W, C)
+        act = (vp(a.data), vp(a.ab[0]), vp(a.ab[1]), int(a.relu))
         if a.oc_fused is not None:
-            return self._bn_backward_oc(prec, a, grads)
-        gate = None
-        if a.gate_fused is not None:
-            # the gate's deferred gradient is the only other contribution and a pooled gradient is folded in: both
-            # passes form it on the fly; otherwise it is stored first, by the launch that was deferred
-            if pool is not None and fused is None and not os.environ.get("UNET_NO_GATE_BN_FUSE"):
+            # OutConv's input: the sums came from unet_outconv_bwd_bn, the apply recomputes OutConv's input
+            # gradient from the logit gradient
+            oc, a.oc_fused = a.oc_fused, None
+            reduce, apply, sums = None, "unet_bn_bwd_apply_oc", (oc.part, oc.rows)
+            ops = (*geo, oc.k, *act, vp(oc.w), vp(oc.dl))
+        else:
+            pool, gate = a.pool_grad, None
+            if a.gate_fused is not None and pool is not None and sums is None \
+                    and not os.environ.get("UNET_NO_GATE_BN_FUSE"):
+                # the gate's pending gradient is the only other contribution and a pooled gradient is folded in:
+                # both passes form it on the fly (otherwise has_grad() stores it)
                 gate, a.gate_fused = a.gate_fused, None
+            has = a.has_grad()
+            assert has or pool is not None, "activation gradient missing"
+            gcode = {torch.bfloat16: L.BF16, torch.float16: L.F16}.get(a.grad.dtype, L.F32) if has else L.F32
+            if pool is None:
+                reduce, apply = "unet_bn_bwd_reduce", "unet_bn_bwd_apply"
+                ops = (prec.code, gcode, P, C, vp(a.grad), *act)
             else:
-                a.flush_gate()
-        assert a.has_grad() or pool is not None, "activation gradient missing"
-        gcode = {torch.bfloat16: L.BF16, torch.float16: L.F16}.get(a.grad.dtype, L.F32) if a.has_grad() else L.F32
-        if pool is not None:
-            # a Down block's input: its MaxPool2d backward is folded into both passes (the pooled dgrad is
-            # routed by the argmax codes and added after the other consumers' fp32 sum)
-            assert fused is None and gcode == L.F32
-            g2, code, ph, pw = pool
-            da = vp(a.grad) if a.has_grad() else None
+                # a Down block's input: its MaxPool2d backward is folded into both passes (the pooled dgrad is
+                # routed by the argmax codes and added after the other consumers' fp32 sum)
+                assert sums is None and gcode == L.F32
+                a.pool_grad = None
+                pooled = (vp(pool.g2), vp(pool.code), pool.ph, pool.pw, *act)
+                if gate is None:
+                    reduce, apply = "unet_bn_bwd_reduce_pool", "unet_bn_bwd_apply_pool"
+                    ops = (*geo, vp(a.grad) if has else None, *pooled)
+                else:
+                    assert not has
+                    reduce, apply = "unet_bn_bwd_reduce_pool_gate", "unet_bn_bwd_apply_pool_gate"
+                    ops = (*geo, gate.dxw.shape[-1], vp(gate.d_xs), vp(gate.dxw), vp(gate.wt), vp(gate.gate_p),
+                           vp(gate.gate_ab), *pooled)
+        if sums is None:
             rows = L.load().unet_bn_bwd_reduce_rows(P, C)
             part = f32(2, rows, C, device=dev)
-            if gate is not None:
-                assert not a.has_grad()
-                _, d_xs, dxw, gp, gab, wt = gate[:6]
-                gargs = (prec.code, a.N, a.H, a.W, C, dxw.shape[-1], vp(d_xs), vp(dxw), vp(wt), vp(gp), vp(gab),
-                         vp(g2), vp(code), ph, pw, vp(a.data), vp(a.ab[0]), vp(a.ab[1]), int(a.relu))
-                L.call("unet_bn_bwd_reduce_pool_gate", *gargs, vp(a.mean), vp(a.invstd), vp(part), stream())
-            else:
-                L.call("unet_bn_bwd_reduce_pool", prec.code, a.N, a.H, a.W, C, da, vp(g2), vp(code), ph, pw,
-                       vp(a.data), vp(a.ab[0]), vp(a.ab[1]), int(a.relu), vp(a.mean), vp(a.invstd), vp(part),
-                       stream())
-        elif fused is not None:
-            part, rows = fused
+            L.call(reduce, *ops, vp(a.mean), vp(a.invstd), vp(part), stream())
         else:
-            rows = L.load().unet_bn_bwd_reduce_rows(P, C)
-            part = f32(2, rows, C, device=dev)
-            L.call("unet_bn_bwd_reduce", prec.code, gcode, P, C, vp(a.grad), vp(a.data), vp(a.ab[0]),
-                   vp(a.ab[1]), int(a.relu), vp(a.mean), vp(a.invstd), vp(part), stream())
-        dgamma, dbeta, coef = f32(C, device=dev), f32(C, device=dev), f32(3, C, device=dev)
-        L.call("unet_bn_bwd_finalize", vp(part[0]), vp(part[1]), rows, C, P if a.batch_stats else 0, vp(self.bn.weight), vp(a.mean),
-               vp(a.invstd), vp(dgamma), vp(dbeta), 0, vp(coef), stream())
-        grads.put(self.bn.weight, dgamma)
-        grads.put(self.bn.bias, dbeta)
+            part, rows = sums
+        coef = _bn_backward_finalize(self.bn, grads, part[0], part[1], rows, C, P if a.batch_stats else 0, a.mean,
+                                     a.invstd)
         dy = torch.empty(a.N, a.H, a.W, C, dtype=prec.torch_dtype, device=dev)
-        if gate is not None:
-            L.call("unet_bn_bwd_apply_pool_gate", *gargs, vp(coef), vp(dy), stream())
-            a.pool_grad = None
-        elif pool is not None:
-            L.call("unet_bn_bwd_apply_pool", prec.code, a.N, a.H, a.W, C, da, vp(g2), vp(code), ph, pw, vp(a.data),
-                   vp(a.ab[0]), vp(a.ab[1]), int(a.relu), vp(coef), vp(dy), stream())
-            a.pool_grad = None
-        else:
-            L.call("unet_bn_bwd_apply", prec.code, gcode, P, C, vp(a.grad), vp(a.data), vp(a.ab[0]), vp(a.ab[1]),
-                   int(a.relu), vp(coef), vp(dy), stream())
-        return dy
-
-    def _bn_backward_oc(self, prec: Precision, a: Act, grads: Grads) -> torch.Tensor:
-        """BatchNorm2d(+ReLU) backward of OutConv's input: the sums came from unet_outconv_bwd_bn, the apply
-        recomputes OutConv's input gradient from the logit gradient (unet_bn_bwd_apply_oc)."""
-        dl, w, k, part, rows = a.oc_fused
-        a.oc_fused = None
-        dev = a.data.device
-        C = a.C
-        dgamma, dbeta, coef = f32(C, device=dev), f32(C, device=dev), f32(3, C, device=dev)
-        L.call("unet_bn_bwd_finalize", vp(part[0]), vp(part[1]), rows, C, a.pixels if a.batch_stats else 0,
-               vp(self.bn.weight), vp(a.mean), vp(a.invstd), vp(dgamma), vp(dbeta), 0, vp(coef), stream())
-        grads.put(self.bn.weight, dgamma)
-        grads.put(self.bn.bias, dbeta)
-        dy = torch.empty(a.N, a.H, a.W, C, dtype=prec.torch_dtype, device=dev)
-        L.call("unet_bn_bwd_apply_oc", prec.code, a.N, a.H, a.W, C, k, vp(a.data), vp(a.ab[0]), vp(a.ab[1]),
-               int(a.relu), vp(w), vp(dl), vp(coef), vp(dy), stream())
+        L.call(apply, *ops, vp(coef), vp(dy), stream())
         return dy
 
     def conv_backward(self, prec: Precision, dy: torch.Tensor, srcs: List[L.Src], grads: Grads,
-                      dgrad: Optional[dict]):
-        """wgrad into grads[conv.weight]; dgrad routed by `dgrad`:
-        {'mode': 'f32', 'out': t, 'accum': 0/1, 'out2': t2, 'accum2': 0/1, 'split': s}
-        {'mode': 'pool', 'out': t (initialised), 'pool_src': Src}"""
+                      dgrad: Optional[Dgrad]):
+        """wgrad into grads[conv.weight]; the input gradient goes where the `dgrad` route says (None: not
+        formed).  Returns dgrad_launch's result."""
         N, H, W, cout = dy.shape
-        dev = dy.device
-        wd = L.WgradDesc()
-        wd.dtype = prec.code
-        wd.N, wd.H, wd.W, wd.Cin, wd.Cout, wd.ksize = N, H, W, self.cin, self.cout, self.k
-        if self.wsrcs is not None:
-            srcs = self.wsrcs          # the forward's stored copy of its (transformed) input
-        wd.nsrc = len(srcs)
-        for i, s in enumerate(srcs):
-            wd.src[i] = s
-        wd.dy = dy.data_ptr()
-        dw = f32(self.cout, self.cin, self.k, self.k, device=dev)
-        wd.dw = dw.data_ptr()
-        wd.accum = 0
-        ws_bytes = L.load().unet_wgrad_workspace(wd)
-        ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
-        wd.workspace = ws.data_ptr()
-        probe.launch(lambda: wgrad_kernel_name(wd), 2.0 * N * H * W * self.cin * self.cout * self.k ** 2,
-                     lambda: L.call("unet_conv_wgrad", wd, stream()))
+        dw = f32(self.cout, self.cin, self.k, self.k, device=dy.device)
+        # (the forward's stored copy of its transformed input, where it made one)
+        _wgrad(prec, N, H, W, self.cin, self.cout, self.k, self.wsrcs if self.wsrcs is not None else srcs, dy, dw)
         grads.put(self.conv.weight, dw)
         self.wsrcs = self.wact = None
         if dgrad is None:
-            return
-        wt = self.pre_wt if self.pre_wt is not None else pack_weight(self.conv.weight, prec, transpose=True)
-        self.pre_wt = None
-        self.dgrad_launch(prec, dy, wt, dgrad)
+            return None
+        return self.dgrad_launch(prec, dy, self.take_weight(prec, transpose=True), dgrad)
 
-    def dgrad_launch(self, prec: Precision, dy: torch.Tensor, wt: torch.Tensor, dgrad: dict):
-        """The input-gradient launch of conv_backward (wt: the packed transposed weight)."""
+    def dgrad_launch(self, prec: Precision, dy: torch.Tensor, wt: torch.Tensor, dgrad: Dgrad):
+        """The input-gradient launch of conv_backward (wt: the packed transposed weight).  Returns the
+        (partial sums [2][rows][C], rows) of a DgradY route's `bnb` activation, else None."""
         N, H, W, cout = dy.shape
         dev = dy.device
         d = _conv_desc(prec, N, H, W, self.cout, self.cin, self.k, [_plain_src(dy)], wt)
+        d.out = dgrad.out.data_ptr()
         ws = None   # split-K scratch (L.attach_workspace), attached once every other field is set
-        if dgrad["mode"] == "y":
-            # op-dtype gradient, stored; with "bnb" (the Act it is the gradient of) the epilogue also
-            # reduces that activation's BatchNorm-backward sums, returned in dgrad["bnb_part"]
+        sums = None
+        if isinstance(dgrad, DgradY):
             d.out_mode = L.OUT_Y
-            d.out = dgrad["out"].data_ptr()
-            a = dgrad.get("bnb")
+            a = dgrad.bnb
             if a is not None:
                 d.bnb_y, d.bnb_scale, d.bnb_shift = vp(a.data), vp(a.ab[0]), vp(a.ab[1])
                 d.bnb_relu, d.bnb_mean, d.bnb_invstd = int(a.relu), vp(a.mean), vp(a.invstd)
@@ -290,34 +345,37 @@ class ConvBN:
                 rows = L.load().unet_conv_stats_rows(d)
                 part = f32(2, rows, self.cin, device=dev)
                 d.bnb_stats = part.data_ptr()
-                dgrad["bnb_part"] = (part, rows)
-        elif dgrad["mode"] == "f32_gated":
-            # the attention gate's W_x input gradient plus the x*s term: out (+)= s * d(x*s) + W_x^T dy
+                sums = (part, rows)
+        elif isinstance(dgrad, DgradGated):
             d.out_mode = L.OUT_F32_GATED
-            d.out = dgrad["out"].data_ptr()
-            d.accum = int(dgrad.get("accum", 0))
+            d.accum = int(dgrad.accum)
             d.split = self.cin
             ps = L.Src()
             ps.kind, ps.C, ps.H, ps.W = L.SRC_PLAIN, self.cin, H, W
-            ps.data, ps.gate_p, ps.gate_ab = vp(dgrad["dxs"]), vp(dgrad["gate_p"]), vp(dgrad["gate_ab"])
+            ps.data, ps.gate_p, ps.gate_ab = vp(dgrad.dxs), vp(dgrad.gate_p), vp(dgrad.gate_ab)
             d.pool_src = ps
-        elif dgrad["mode"] == "pool":
+        elif isinstance(dgrad, DgradPool):
             d.out_mode = L.OUT_POOL_BWD
-            d.out = dgrad["out"].data_ptr()
-            d.pool_src = dgrad["pool_src"]
-            d.pool_code = vp(dgrad.get("code"))
-        else:
+            d.pool_src = dgrad.pool_src
+            d.pool_code = vp(dgrad.code)
+        elif isinstance(dgrad, DgradF32):
             d.out_mode = L.OUT_F32
-            d.out = dgrad["out"].data_ptr()
-            d.accum = int(dgrad.get("accum", 0))
-            d.split = int(dgrad.get("split", self.cin))
-            o2 = dgrad.get("out2")
-            d.out2 = o2.data_ptr() if o2 is not None else None
-            d.accum2 = int(dgrad.get("accum2", 0))
+            d.accum = int(dgrad.accum)
+            d.split = self.cin if dgrad.split is None else int(dgrad.split)
+            d.out2 = vp(dgrad.out2)
+            d.accum2 = int(dgrad.accum2)
+        else:
+            raise TypeError(f"unet HIP path: unknown dgrad route {dgrad!r}")
         if ws is None:
             ws = L.attach_workspace(d, dev)
         probe.launch(lambda: conv_kernel_name(d), 2.0 * N * H * W * self.cin * self.cout * self.k ** 2,
                      lambda: L.call("unet_conv", d, stream()), d.out_mode)
+        return sums
+
+    def store_gate_grad(self, x: Act, g: GateGrad) -> None:
+        """Act.flush_gate's launch, on the gate's W_x: the gated dgrad that GateStage.backward deferred."""
+        dx, acc = x.grad_target()
+        self.dgrad_launch(g.prec, g.dxw, g.wt, DgradGated(dx, acc, g.d_xs, g.gate_p, g.gate_ab))
 
 
 # ------------------------------------------------------------------------------------------------
@@ -335,7 +393,7 @@ class DoubleConvStage:
         self.a2 = self.c2.forward(prec, [self.a1.src()], N, H, W, training)
         return self.a2
 
-    def backward(self, prec, grads: Grads, dgrad: Optional[dict]):
+    def backward(self, prec, grads: Grads, dgrad: Optional[Dgrad]):
         dy2 = self.c2.bn_backward(prec, self.a2, grads)
         if prec.code != L.F32:
             # the middle activation has one consumer (the second conv): its gradient is written once,
@@ -344,15 +402,12 @@ class DoubleConvStage:
             # BN1's backward sums are reduced by that dgrad's epilogue (no separate pass over g1 and y1)
             g1 = self.a1.grad_single(prec.torch_dtype)
             # (env UNET_NO_BNB_FUSE: A/B switch back to the separate unet_bn_bwd_reduce pass)
-            route = {"mode": "y", "out": g1, "bnb": None if os.environ.get("UNET_NO_BNB_FUSE") else self.a1}
-            self.c2.conv_backward(prec, dy2, [self.a1.src()], grads, route)
-            fused = route.get("bnb_part")
+            route = DgradY(g1, None if os.environ.get("UNET_NO_BNB_FUSE") else self.a1)
         else:
-            g1, acc = self.a1.grad_target()
-            self.c2.conv_backward(prec, dy2, [self.a1.src()], grads, {"mode": "f32", "out": g1, "accum": acc})
-            fused = None
+            route = DgradF32(*self.a1.grad_target())
+        sums = self.c2.conv_backward(prec, dy2, [self.a1.src()], grads, route)
         del dy2
-        dy1 = self.c1.bn_backward(prec, self.a1, grads, fused)
+        dy1 = self.c1.bn_backward(prec, self.a1, grads, sums)
         self.c1.conv_backward(prec, dy1, self.srcs, grads, dgrad)
 
 
@@ -368,14 +423,6 @@ class DoubleConvStage:
 # route is measured at the bench maps only, and the equivalence tests of the gated dgrad
 # (tests/test_gpu_fusion_equivalence.py) watch its launch at 2 x 128^2 and 2 x 98^2.
 GATE_BN_FUSE_LEVELS = {64: 65536, 128: 16384}
-
-
-def _store_gate_grad(x: Act, d_xs, dxw, gate_p, gate_ab, wt, cx, prec) -> None:
-    """Act.flush_gate's worker: the f32_gated W_x dgrad that GateStage.backward deferred, as the first
-    contribution to x.grad."""
-    dx, acc = x.grad_target()
-    cx.dgrad_launch(prec, dxw, wt, {"mode": "f32_gated", "out": dx, "accum": acc, "dxs": d_xs, "gate_p": gate_p,
-                                    "gate_ab": gate_ab})
 
 
 class GateStage:
@@ -418,26 +465,14 @@ class GateStage:
         use_batch = training or not bn.track_running_stats
         self.psi_batch = use_batch
         self.psi_mean, self.psi_invstd = f32(1, device=dev), f32(1, device=dev)
-        if use_batch:
-            upd = training and bn.track_running_stats
-            mom = -1.0 if bn.momentum is None else float(bn.momentum)
-            L.call("unet_bn_finalize", vp(part), rows, 1, P, vp(bn.weight), vp(bn.bias),
-                   vp(bn.running_mean) if upd else None, vp(bn.running_var) if upd else None,
-                   vp(bn.num_batches_tracked) if upd else None, mom, float(bn.eps), vp(self.psi_mean),
-                   vp(self.psi_invstd), vp(self.psi_ab[0]), vp(self.psi_ab[1]), stream())
-        else:
-            L.call("unet_bn_eval_affine", 1, vp(bn.weight), vp(bn.bias), vp(bn.running_mean), vp(bn.running_var),
-                   float(bn.eps), vp(self.psi_ab[0]), vp(self.psi_ab[1]), vp(self.psi_mean), vp(self.psi_invstd),
-                   stream())
+        _bn_forward_stats(bn, training, use_batch, part, rows, 1, P, self.psi_mean, self.psi_invstd, self.psi_ab)
 
     def _forward_eval(self, prec, g_up_t: torch.Tensor, x: Act):
         """Eval mode, no autograd (predict.py): BN on running statistics, so psi's pre-activation is
         computed in one pass from g_up and x (unet_gate_psi_eval) without storing W_g(g) / W_x(x)."""
         dev = x.data.device
         ci = self.ci
-        wg = self.cg.pre_wp if self.cg.pre_wp is not None else pack_weight(self.cg.conv.weight, prec, False)
-        wx = self.cx.pre_wp if self.cx.pre_wp is not None else pack_weight(self.cx.conv.weight, prec, False)
-        self.cg.pre_wp = self.cx.pre_wp = None
+        wg, wx = self.cg.take_weight(prec, transpose=False), self.cx.take_weight(prec, transpose=False)
         gab, xab = f32(2, ci, device=dev), f32(2, ci, device=dev)
         for bn, ab in ((self.cg.bn, gab), (self.cx.bn, xab)):
             L.call("unet_bn_eval_affine", ci, vp(bn.weight), vp(bn.bias), vp(bn.running_mean), vp(bn.running_var),
@@ -474,12 +509,8 @@ class GateStage:
         part1 = f32(2, rows1, device=dev)
         L.call("unet_gate_bwd1", prec.code, P, Cx, vp(d_xs), vp(x.data), vp(x.ab[0]), vp(x.ab[1]), int(x.relu), vp(self.p),
                vp(self.psi_ab), vp(self.psi_mean), vp(self.psi_invstd), vp(dx), dx_acc, vp(dq), vp(part1), stream())
-        dgp, dbp, pcoef = f32(1, device=dev), f32(1, device=dev), f32(3, device=dev)
-        L.call("unet_bn_bwd_finalize", vp(part1[0]), vp(part1[1]), rows1, 1, P if self.psi_batch else 0,
-               vp(self.psi_bn.weight),
-               vp(self.psi_mean), vp(self.psi_invstd), vp(dgp), vp(dbp), 0, vp(pcoef), stream())
-        grads.put(self.psi_bn.weight, dgp)
-        grads.put(self.psi_bn.bias, dbp)
+        pcoef = _bn_backward_finalize(self.psi_bn, grads, part1[0], part1[1], rows1, 1, P if self.psi_batch else 0,
+                                      self.psi_mean, self.psi_invstd)
         # (2) psi conv / relu / both BN backward sums
         rows2 = L.load().unet_gate_bwd2_rows(P, Ci)
         part2 = f32(4, rows2, Ci, device=dev)
@@ -508,31 +539,17 @@ class GateStage:
                vp(self.xw.ab), vp(self.wpsi), vp(dq), vp(self.p), vp(pcoef), vp(gcoef), vp(xcoef), vp(dgw), vp(dxw),
                stream())
         # (4) the two 1x1 projections
-        wt_g = None
-        if defer_g:
-            wt_g = self.cg.pre_wt if self.cg.pre_wt is not None else pack_weight(self.cg.conv.weight, prec,
-                                                                                 transpose=True)
-            self.cg.pre_wt = None
-            self.cg.conv_backward(prec, dgw, self.gw_src, grads, None)
-        else:
-            self.cg.conv_backward(prec, dgw, self.gw_src, grads,
-                                  {"mode": "f32", "out": d_gup, "accum": d_gup_accum})
+        wt_g = self.cg.take_weight(prec, transpose=True) if defer_g else None
+        self.cg.conv_backward(prec, dgw, self.gw_src, grads, None if defer_g else DgradF32(d_gup, d_gup_accum))
         if fuse and self._bn_fused_ok(prec, x):
-            # dx is not stored: the pooled BN backward of x forms it from these operands (unet_bn_bwd_*_pool_gate);
-            # whatever else touches x's gradient first stores it with the launch deferred here (Act.flush_gate)
-            wt_x = self.cx.pre_wt if self.cx.pre_wt is not None else pack_weight(self.cx.conv.weight, prec,
-                                                                                 transpose=True)
-            self.cx.pre_wt = None
+            # dx is not stored: the pooled BN backward of x forms it from these operands (unet_bn_bwd_*_pool_gate)
+            wt_x = self.cx.take_weight(prec, transpose=True)
             self.cx.conv_backward(prec, dxw, [x.src()], grads, None)
-            x.gate_fused = (_store_gate_grad, d_xs, dxw, self.p, self.psi_ab, wt_x, self.cx, prec)
-            return (dgw, wt_g) if defer_g else None
-        dx2, acc2 = x.grad_target()
-        if fuse:
-            self.cx.conv_backward(prec, dxw, [x.src()], grads, {"mode": "f32_gated", "out": dx2, "accum": acc2,
-                                                                "dxs": d_xs, "gate_p": self.p,
-                                                                "gate_ab": self.psi_ab})
+            x.gate_fused = GateGrad(d_xs, dxw, self.p, self.psi_ab, wt_x, self.cx, prec)
         else:
-            self.cx.conv_backward(prec, dxw, [x.src()], grads, {"mode": "f32", "out": dx2, "accum": acc2})
+            dx2, acc2 = x.grad_target()
+            route = DgradGated(dx2, acc2, d_xs, self.p, self.psi_ab) if fuse else DgradF32(dx2, acc2)
+            self.cx.conv_backward(prec, dxw, [x.src()], grads, route)
         return (dgw, wt_g) if defer_g else None
 
     def up_fused_ok(self, prec, g: Act, x: Act) -> bool:
@@ -552,13 +569,7 @@ class GateStage:
         # kernel whose bits the fused call has
         if min(x.H, x.W) <= 8:
             return False
-        d = L.ConvDesc()
-        d.dtype, d.N, d.H, d.W, d.Cin, d.Cout, d.ksize, d.nsrc = prec.code, x.N, x.H, x.W, self.ci, g.C, 1, 1
-        s = L.Src()
-        s.kind, s.C, s.H, s.W = L.SRC_PLAIN, self.ci, x.H, x.W
-        d.src[0] = s
-        d.out_mode, d.split, d.accum = L.OUT_F32, g.C, 1
-        if not conv_kernel_name(d).startswith("pw_conv_kernel"):
+        if not _pw_kernel_serves(prec, x, self.ci, g.C, L.OUT_F32, accum=1):
             return False
         return bool(L.load().unet_upsample_bwd_pw_ok(prec.code, g.N, g.C, g.H, g.W, x.H, x.W, 0, 0, x.H, x.W,
                                                      up_scale(g.H, x.H), up_scale(g.W, x.W), self.ci))
@@ -569,10 +580,8 @@ class GateStage:
         ConvBN's output that DownStage.backward will hand a folded pooled gradient (its conditions)."""
         if os.environ.get("UNET_NO_GATE_BN_FUSE") or os.environ.get("UNET_NO_POOL_FOLD"):   # (env: A/B switches)
             return False
-        cv = x.C // 8
         if not (x.bn_owned and x.ab is not None and not x.has_grad() and x.grad is None and x.pool_grad is None
-                and x.oc_fused is None and x.gate_fused is None and x.C % 8 == 0 and cv <= 256
-                and cv & (cv - 1) == 0 and x.pixels < 2 ** 31):
+                and x.oc_fused is None and x.gate_fused is None and _chan_vec_ok(x.C, 8) and x.pixels < 2 ** 31):
             return False
         if x.pixels < GATE_BN_FUSE_LEVELS.get(x.C, 2 ** 31):
             return False
@@ -582,13 +591,7 @@ class GateStage:
         """Whether the W_x dgrad (Ci -> Cx 1x1) runs on the kernel that serves UNET_OUT_F32_GATED."""
         if prec.code not in (L.BF16, L.F16) or os.environ.get("UNET_NO_GATE_FUSE"):   # (env: A/B switch)
             return False
-        d = L.ConvDesc()
-        d.dtype, d.N, d.H, d.W, d.Cin, d.Cout, d.ksize, d.nsrc = prec.code, x.N, x.H, x.W, self.ci, x.C, 1, 1
-        s = L.Src()
-        s.kind, s.C, s.H, s.W = L.SRC_PLAIN, self.ci, x.H, x.W
-        d.src[0] = s
-        d.out_mode, d.split = L.OUT_F32_GATED, x.C
-        return conv_kernel_name(d).startswith("pw_conv_kernel")
+        return _pw_kernel_serves(prec, x, self.ci, x.C, L.OUT_F32_GATED, accum=0)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -661,19 +664,8 @@ class ConvTStage:
             L.call("unet_colsum", vp(part), rows, ct, vp(db), 0, stream())
             grads.put(self.m.bias, db)
         # weight gradient of the equivalent 1x1 conv, back to the ConvTranspose2d layout [Cin][Ct][2][2]
-        wd = L.WgradDesc()
-        wd.dtype = prec.code
-        wd.N, wd.H, wd.W, wd.Cin, wd.Cout, wd.ksize = N, h, w, self.cin, 4 * ct, 1
-        wd.nsrc = 1
-        wd.src[0] = x1.src()
-        wd.dy = dys.data_ptr()
         dw4 = f32(4 * ct, self.cin, device=dev)
-        wd.dw = dw4.data_ptr()
-        wd.accum = 0
-        ws = torch.empty(max(L.load().unet_wgrad_workspace(wd), 16), dtype=torch.uint8, device=dev)
-        wd.workspace = ws.data_ptr()
-        probe.launch(lambda: wgrad_kernel_name(wd), 2.0 * P * self.cin * 4 * ct,
-                     lambda: L.call("unet_conv_wgrad", wd, stream()))
+        _wgrad(prec, N, h, w, self.cin, 4 * ct, 1, [x1.src()], dys, dw4)
         grads.put(self.m.weight, dw4.view(2, 2, ct, self.cin).permute(3, 2, 0, 1).contiguous())
         if not need_dx:
             return
@@ -713,8 +705,9 @@ class UpStage:
             # bilinear x2 of relu(bn(x1)), padded into the skip's frame, written once (layers.py:78,98-102)
             up_t = _materialize(prec, x1.src_up(up_h, up_w, pt, pl), x2.N, x2.H, x2.W)
             self.up_t = up_t
+        # the bilinear map already has the skip's frame: it is the gate's g_up too (layers.py:183)
+        self.same = same = up_t is not None and up_h == x2.H and up_w == x2.W and pt == 0 and pl == 0
         if self.gate is not None:
-            same = up_t is not None and up_h == x2.H and up_w == x2.W and pt == 0 and pl == 0
             self.gate.forward(prec, x1, x2, training, g_up=_plain_src(up_t) if same else None,
                               g_up_t=up_t if same and eval_only else None)
             skip = self.gate.gated_src()
@@ -735,10 +728,8 @@ class UpStage:
         d_up = f32(x2.N, x2.H, x2.W, cu, device=dev)
         if self.gate is not None:
             d_xs = f32(x2.N, x2.H, x2.W, x2.C, device=dev)
-            self.dc.backward(prec, grads, {"mode": "f32", "out": d_xs, "accum": 0, "out2": d_up, "accum2": 0,
-                                           "split": x2.C})
-            same = (self.convt is None and up_h == x2.H and up_w == x2.W and pt == 0 and pl == 0)
-            if same and self.gate.up_fused_ok(prec, x1, x2):
+            self.dc.backward(prec, grads, DgradF32(d_xs, 0, d_up, 0, x2.C))
+            if self.same and self.gate.up_fused_ok(prec, x1, x2):
                 # d_up + W_g^T dgw is formed as the adjoint loads d_up: no read-modify-write pass over d_up
                 dgw, wt_g = self.gate.backward(prec, d_xs, grads, None, 0, defer_g=True)
                 gx, acc = x1.grad_target()
@@ -746,7 +737,7 @@ class UpStage:
                        up_scale(x1.H, up_h), up_scale(x1.W, up_w), vp(d_up), vp(dgw), self.gate.ci, vp(wt_g),
                        vp(gx), acc, stream())
                 return
-            if same:
+            if self.same:
                 self.gate.backward(prec, d_xs, grads, d_up, 1)
             else:
                 d_gup = f32(x2.N, x2.H, x2.W, x1.C, device=dev)
@@ -756,8 +747,7 @@ class UpStage:
                        up_scale(x1.H, x2.H), up_scale(x1.W, x2.W), vp(d_gup), vp(gx), acc, stream())
         else:
             g2, acc2 = x2.grad_target()
-            self.dc.backward(prec, grads, {"mode": "f32", "out": g2, "accum": acc2, "out2": d_up, "accum2": 0,
-                                           "split": x2.C})
+            self.dc.backward(prec, grads, DgradF32(g2, acc2, d_up, 0, x2.C))
         if self.convt is not None:
             self.convt.backward(prec, d_up, pt, pl, grads)
             return
@@ -778,9 +768,7 @@ class DownStage:
         h, w = x.H // 2, x.W // 2
         self.xp = torch.empty(x.N, h, w, x.C, dtype=prec.torch_dtype, device=x.data.device)
         self.code = None
-        vec = 8 if prec.code != L.F32 else 4
-        cv = x.C // vec
-        if x.C % vec == 0 and cv <= 256 and cv & (cv - 1) == 0:
+        if _chan_vec_ok(x.C, 8 if prec.code != L.F32 else 4):
             # the 2x2 argmax is recorded too: the pool backward then routes by one byte per element
             self.code = torch.empty(x.N, h, w, x.C, dtype=torch.uint8, device=x.data.device)
             L.call("unet_materialize_pool", prec.code, x.src_pool(), x.N, h, w, vp(self.xp), vp(self.code), stream())
@@ -790,8 +778,7 @@ class DownStage:
 
     def backward(self, prec, grads: Grads):
         x = self.x
-        cv = x.C // 8
-        if self.code is not None and x.bn_owned and x.C % 8 == 0 and cv <= 256 and cv & (cv - 1) == 0 \
+        if self.code is not None and x.bn_owned and _chan_vec_ok(x.C, 8) \
                 and not os.environ.get("UNET_NO_POOL_FOLD") \
                 and x.pixels < 2 ** 31 and x.pool_grad is None and (x.grad is None or x.grad.dtype == torch.float32):
             # the dgrad is written at the pooled resolution (plain fp32 stores); the producer's BatchNorm
@@ -799,11 +786,11 @@ class DownStage:
             # (unet_bn_bwd_reduce_pool / _apply_pool), so the full-resolution map is never read-modified
             h, w = self.xp.shape[1], self.xp.shape[2]
             g2 = f32(x.N, h, w, x.C, device=x.data.device)
-            self.dc.backward(prec, grads, {"mode": "f32", "out": g2, "accum": 0})
-            x.pool_grad = (g2, self.code, h, w)
+            self.dc.backward(prec, grads, DgradF32(g2))
+            x.pool_grad = PoolGrad(g2, self.code, h, w)
             return
         g = x.grad_zeroed()
-        self.dc.backward(prec, grads, {"mode": "pool", "out": g, "pool_src": x.src_pool(), "code": self.code})
+        self.dc.backward(prec, grads, DgradPool(g, x.src_pool(), self.code))
 
 
 class OutConvStage:
@@ -831,9 +818,8 @@ class OutConvStage:
         dl = dlogits.float().contiguous()
         rows = L.load().unet_outconv_rows(a.pixels)
         part = f32(rows, self.k + 1, max(a.C, self.k), device=dev)
-        cv = a.C // 8
         if (self.sole_consumer and a.bn_owned and not a.has_grad() and a.pool_grad is None and self.k == 2
-                and a.C % 8 == 0 and cv <= 256 and cv & (cv - 1) == 0 and a.pixels < 2 ** 31
+                and _chan_vec_ok(a.C, 8) and a.pixels < 2 ** 31
                 and not os.environ.get("UNET_NO_OC_FUSE")):
             # OutConv is the activation's only consumer: its gradient W^T dl is not stored; the BN-backward sums
             # are taken here and the BN apply recomputes it (unet_outconv_bwd_bn / unet_bn_bwd_apply_oc)
@@ -841,7 +827,7 @@ class OutConvStage:
             L.call("unet_outconv_bwd_bn", prec.code, a.N, a.H, a.W, a.C, self.k, vp(a.data), vp(a.ab[0]),
                    vp(a.ab[1]), int(a.relu), vp(self.w), vp(dl), vp(a.mean), vp(a.invstd), vp(part), vp(bpart),
                    stream())
-            a.oc_fused = (dl, self.w, self.k, bpart, rows)
+            a.oc_fused = OutConvGrad(dl, self.w, self.k, bpart, rows)
         else:
             g, acc = a.grad_target()
             L.call("unet_outconv_bwd", prec.code, a.N, a.H, a.W, a.C, self.k, vp(a.data), vp(a.ab[0]), vp(a.ab[1]),
@@ -937,7 +923,7 @@ class NetworkPlan:
 
     def fwd_inc(self):
         N, C, H, W = self.x.shape
-        self.xs = [self.inc.forward(self.prec, [_nchw(self.x)], N, H, W, self.training, keep=self.x)]
+        self.xs = [self.inc.forward(self.prec, [nchw_src(self.x)], N, H, W, self.training, keep=self.x)]
 
     def fwd_down(self, i: int):
         self.xs.append(self.downs[i].forward(self.prec, self.xs[-1], self.training))
@@ -1006,11 +992,5 @@ class NetworkPlan:
         x = self.x
         N, C, H, W = x.shape
         gx = f32(N, H, W, C, device=x.device)
-        self.inc.backward(self.prec, grads, {"mode": "f32", "out": gx, "accum": 0})
-        from .runtime import grad_nhwc_to_nchw
+        self.inc.backward(self.prec, grads, DgradF32(gx))
         return grad_nhwc_to_nchw(gx)
-
-
-def _nchw(x: torch.Tensor) -> L.Src:
-    from .runtime import nchw_src
-    return nchw_src(x)
