@@ -337,6 +337,19 @@ int unet_bn_bwd_apply_oc(int dtype, long long N, int H, int W, int C, int K, con
                          void* stream);
 int unet_outconv_bwd_finalize(const float* partial, int rows, int C, int K, float* dw, float* db,
                               int accum, void* stream);
+/* OutConv for 9..16 classes on MFMA (outconv_mc.hip).  Arguments as unet_outconv_fwd / unet_outconv_bwd; `partial`
+ * is the same table ([unet_outconv_rows(P)][K+1][C], db in row K) and goes to unet_outconv_bwd_finalize unchanged.
+ * Operand convention of the conv kernels: act(y) = relu?(fmaf(y, scale, shift)) rounded to the operand type, w and
+ * dl rounded to it where they enter an MFMA, fp32 accumulation, db from the unrounded dl; nothing is rounded in
+ * UNET_F32 mode.  unet_outconv_mc_ok: 1 when served (9 <= K <= 16, C % 8 == 0, 16 <= C <= 512); anything else
+ * returns UNET_ERR_UNSUPPORTED before a launch.                                                            */
+int unet_outconv_mc_ok(int dtype, int C, int K);
+int unet_outconv_mc_fwd(int dtype, long long N, int H, int W, int C, int K, const void* y, const float* scale,
+                        const float* shift, int relu, const float* w, const float* b, float* logits_nchw,
+                        void* stream);
+int unet_outconv_mc_bwd(int dtype, long long N, int H, int W, int C, int K, const void* y, const float* scale,
+                        const float* shift, int relu, const float* w, const float* dlogits_nchw, float* da,
+                        int da_accum, float* partial, void* stream);
 
 /* ---- layout ---------------------------------------------------------------------------------- */
 /* NCHW fp32 <-> NHWC (op dtype / fp32) for standalone module calls                                */

@@ -10,7 +10,7 @@
 
 namespace unet {
 
-constexpr int CM_MAXK = 8;
+constexpr int CM_MAXK = 16;
 
 // z: fp32 NCHW logits [N][C][HW] (labels == nullptr), or labels: int64 [N][HW] predicted classes.
 // EXT = 0: confusion[t, p] for 0 <= t, p < K (SegmentationMetrics.update).  EXT = 1: a (K+1) x (K+1)
@@ -80,7 +80,7 @@ extern "C" int unet_confusion_matrix(long long N, int C, int K, long long HW, co
                                      int has_ignore, int64_t* confusion, void* stream) {
   if (N <= 0 || HW <= 0 || K < 1 || K > CM_MAXK || (logits && C < 1) || (!logits && !labels) || !targets ||
       !confusion) {
-    set_error("unet_confusion_matrix: bad arguments (1 <= num_classes <= 8, C >= 1)");
+    set_error("unet_confusion_matrix: bad arguments (1 <= num_classes <= 16, C >= 1)");
     return UNET_ERR_ARG;
   }
   return launch_confusion(0, N, C, K, HW, logits, labels, targets, ignore_index, has_ignore, confusion, stream);
@@ -91,7 +91,7 @@ extern "C" int unet_confusion_matrix_ext(long long N, int C, int K, long long HW
                                          void* stream) {
   if (N <= 0 || HW <= 0 || K < 1 || K > CM_MAXK || (logits && C < 1) || (!logits && !labels) || !targets ||
       !confusion) {
-    set_error("unet_confusion_matrix_ext: bad arguments (1 <= num_classes <= 8, C >= 1)");
+    set_error("unet_confusion_matrix_ext: bad arguments (1 <= num_classes <= 16, C >= 1)");
     return UNET_ERR_ARG;
   }
   return launch_confusion(1, N, C, K, HW, logits, labels, targets, 0, 0, confusion, stream);

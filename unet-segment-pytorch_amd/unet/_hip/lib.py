@@ -141,6 +141,11 @@ _SIGS = {
     "unet_bn_bwd_apply_oc": (c_int, [c_int, c_ll, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_vp,
                                      c_vp, c_vp]),
     "unet_outconv_bwd_finalize": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_int, c_vp]),
+    "unet_outconv_mc_ok": (c_int, [c_int, c_int, c_int]),
+    "unet_outconv_mc_fwd": (c_int, [c_int, c_ll, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_vp,
+                                    c_vp]),
+    "unet_outconv_mc_bwd": (c_int, [c_int, c_ll, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_vp,
+                                    c_int, c_vp, c_vp]),
     "unet_nchw_to_nhwc": (c_int, [c_int, c_ll, c_int, c_int, c_int, c_vp, c_vp, c_vp]),
     "unet_nhwc_to_nchw": (c_int, [c_int, c_ll, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_int, c_vp, c_vp]),
     "unet_gated_to_nchw": (c_int, [c_int, c_ll, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp]),
@@ -182,7 +187,7 @@ _guard = None
 _NO_LAUNCH = {"unet_last_error", "unet_version", "unet_conv_mtiles", "unet_conv_stats_rows", "unet_conv_variant",
               "unet_wgrad_variant", "unet_conv_act_out_ok", "unet_conv_workspace", "unet_packed_weight_elems", "unet_wgrad_workspace",
               "unet_bn_bwd_reduce_rows", "unet_gate_psi_rows", "unet_gate_bwd2_rows", "unet_convt_bwd_rows",
-              "unet_outconv_rows", "unet_loss_rows", "unet_upsample_bwd_pw_ok", "unet_bn_bwd_pool_gate_ok"}
+              "unet_outconv_rows", "unet_outconv_mc_ok", "unet_loss_rows", "unet_upsample_bwd_pw_ok", "unet_bn_bwd_pool_gate_ok"}
 
 
 class HipLibraryError(RuntimeError):

@@ -802,13 +802,24 @@ class OutConvStage:
         # True for the network's OutConv: the last decoder activation feeds nothing else (unet.py:92, 203)
         self.sole_consumer = sole_consumer
 
+    def _entry(self, prec, a: Act, which: str) -> str:
+        """n_classes <= 8: the misc.hip kernels; 9..16: the MFMA kernels of outconv_mc.hip (entry points of their
+        own; nothing falls back from one to the other)."""
+        if self.k <= 8:
+            return f"unet_outconv_{which}"
+        if not L.load().unet_outconv_mc_ok(prec.code, a.C, self.k):
+            raise RuntimeError(f"OutConv with n_classes = {self.k} > 8 runs on the multi-class MFMA kernels, which need "
+                               f"n_classes <= 16 and an input with C % 8 == 0 and 16 <= C <= 512 channels (got C = {a.C})")
+        return f"unet_outconv_mc_{which}"
+
     def forward(self, prec, a: Act) -> torch.Tensor:
         self.a = a
         dev = a.data.device
+        fwd = self._entry(prec, a, "fwd")
         out = f32(a.N, self.k, a.H, a.W, device=dev)
         self.w = self.conv.weight.detach().reshape(self.k, -1).float().contiguous()
         b = self.conv.bias.detach().float().contiguous()
-        L.call("unet_outconv_fwd", prec.code, a.N, a.H, a.W, a.C, self.k, vp(a.data), vp(a.ab[0]), vp(a.ab[1]),
+        L.call(fwd, prec.code, a.N, a.H, a.W, a.C, self.k, vp(a.data), vp(a.ab[0]), vp(a.ab[1]),
                int(a.relu), vp(self.w), vp(b), vp(out), stream())
         return out
 
@@ -830,8 +841,8 @@ class OutConvStage:
             a.oc_fused = OutConvGrad(dl, self.w, self.k, bpart, rows)
         else:
             g, acc = a.grad_target()
-            L.call("unet_outconv_bwd", prec.code, a.N, a.H, a.W, a.C, self.k, vp(a.data), vp(a.ab[0]), vp(a.ab[1]),
-                   int(a.relu), vp(self.w), vp(dl), vp(g), acc, vp(part), stream())
+            L.call(self._entry(prec, a, "bwd"), prec.code, a.N, a.H, a.W, a.C, self.k, vp(a.data), vp(a.ab[0]),
+                   vp(a.ab[1]), int(a.relu), vp(self.w), vp(dl), vp(g), acc, vp(part), stream())
         dw, db = f32(self.k, a.C, 1, 1, device=dev), f32(self.k, device=dev)
         L.call("unet_outconv_bwd_finalize", vp(part), rows, a.C, self.k, vp(dw), vp(db), 0, stream())
         grads.put(self.conv.weight, dw)

@@ -7,7 +7,8 @@ the means, :131-135).  The difference is where the counting runs: the reference 
 host and walks the pixels in a Python loop (metrics.py:78-84); here `update` is one HIP launch
 (`unet_confusion_matrix`: argmax over the logits + LDS histogram + 64-bit atomics) that accumulates into
 a device tensor without synchronising, and only `compute()` / `get_confusion_matrix()` read it back.
-Counts are integers, so the matrix is bit-identical to the reference's.
+Counts are integers, so the matrix is bit-identical to the reference's.  The kernel's per-workgroup histogram
+holds up to 16 classes (1 <= num_classes <= 16, the loss kernels' range); more are refused with an error.
 
 `compute_iou` / `compute_dice` (metrics.py:160-231) are built on the same kernel.
 """
