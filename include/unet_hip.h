@@ -28,8 +28,9 @@ extern "C" {
 
 /* unet_version() of a library built from this header.  110: unet_conv_desc gained `workspace` (round 5);
  * a caller built against an older header must not pass its (shorter) descriptors to this library.
- * 111: unet_aug_params, unet_aug_elastic_field and unet_aug_apply added (no existing layout changed) */
-#define UNET_ABI_VERSION 113
+ * 111: unet_aug_params, unet_aug_elastic_field and unet_aug_apply added (no existing layout changed)
+ * 114: the optimizer tail (unet_optim_*, unet_ema_update) added (no existing layout changed) */
+#define UNET_ABI_VERSION 114
 
 enum { UNET_F32 = 0, UNET_BF16 = 1, UNET_F16 = 2 };  /* operand (activation / weight) type */
 enum { UNET_ERR_ARG = 1001, UNET_ERR_UNSUPPORTED = 1002 };
@@ -472,6 +473,61 @@ int unet_aug_apply(long long N, int S, const uint8_t* img, int mask_h, int mask_
                    const int32_t* ytab, const int32_t* xtab, const unet_aug_params* table, long long table_len,
                    const float* field, int n_elastic, float mean, float stdv, float* out_img, int64_t* out_mask,
                    void* stream);
+
+/* ---- optimizer tail: clip + AdamW step and ModelEMA (csrc/optim.hip) ----------- */
+/* A multi-tensor update over a device *segment table* (one entry per tensor) and a *chunk map* (one entry per
+ * UNET_OPTIM_CHUNK elements of a tensor; a shorter tensor is one chunk).  One workgroup serves one map entry, so
+ * the chunk boundaries, and with them every sum, depend on the table alone, never on the grid.            */
+#define UNET_OPTIM_CHUNK 8192      /* fp32 elements per chunk (COPY segments: 4 * UNET_OPTIM_CHUNK bytes)    */
+enum {
+  UNET_OPT_ACTIVE = 1,             /* the tensor takes part in this step (it has a gradient)                 */
+  UNET_OPT_ALIGNED = 2,            /* every pointer of the entry is 16-byte aligned: 16-byte accesses; else
+                                      the whole segment takes the element-wise path                          */
+  UNET_OPT_ADAMW = 0 << 4,         /* kind (flags & UNET_OPT_KIND_MASK)                                      */
+  UNET_OPT_EMA = 1 << 4,           /* p <- d*p + (1-d)*g       (p: the EMA tensor, g: the model's)           */
+  UNET_OPT_COPY = 2 << 4,          /* p <- g, numel BYTES      (buffers of any dtype)                        */
+  UNET_OPT_KIND_MASK = 3 << 4
+};
+typedef struct unet_optim_seg {
+  void* p;                /* ADAMW: parameter (fp32); EMA: averaged tensor (fp32); COPY: destination         */
+  const void* g;          /* ADAMW: gradient (fp32); EMA: model parameter (fp32); COPY: source               */
+  float* m;               /* ADAMW: exp_avg                                                                  */
+  float* v;               /* ADAMW: exp_avg_sq                                                               */
+  float* step;            /* ADAMW: the parameter's step count, a device fp32 scalar (torch's capturable layout) */
+  long long numel;        /* elements (COPY: bytes)                                                          */
+  int group;              /* ADAMW: index into the group block                                               */
+  int flags;              /* UNET_OPT_*                                                                      */
+} unet_optim_seg;
+typedef struct unet_optim_chunk { int seg, chunk; } unet_optim_chunk;  /* elements [chunk*CHUNK, +CHUNK) of seg */
+typedef struct unet_optim_group {   /* one torch param_group; doubles, as torch forms its scalars in double   */
+  double lr, beta1, beta2, eps, weight_decay;
+  const float* lr_ptr;    /* not NULL: lr is this device fp32 scalar (a tensor lr) and `lr` is ignored        */
+} unet_optim_group;
+/* chunks of a tensor of numel elements: max(1, ceil(numel / UNET_OPTIM_CHUNK))                             */
+int unet_optim_chunks(long long numel);
+/* pass 1 of torch.nn.utils.clip_grad_norm_ (scripts/train.py:140-141, 154-155): partial[c] (double) = the sum of
+ * squares of chunk c's gradient elements (0 for an inactive or non-ADAMW entry).  No atomics.              */
+int unet_optim_gradnorm(const unet_optim_seg* segs, const unet_optim_chunk* map, int nchunks, double* partial,
+                        void* stream);
+/* the scalars of the step, one workgroup (clip_grad_norm_'s coefficient, GradScaler's unscale and inf check,
+ * AdamW's step count and bias corrections; scripts/train.py:140-142): with S = sum of partial[0..nchunks) in a
+ * fixed order (nchunks == 0: no norm pass ran), inv_scale = 1 / *grad_scale (1 when NULL),
+ *   total_norm = sqrt(S) * inv_scale;  found_inf = (found_inf_in && *found_inf_in != 0) || !isfinite(total_norm);
+ *   coef = inv_scale * (max_norm > 0 ? min(1, max_norm / (total_norm + 1e-6)) : 1);
+ * result[0..3) = {total_norm, found_inf, coef} (fp32).  Unless found_inf, every ACTIVE ADAMW entry i has its
+ * *step advanced by one and bc[i] = {1 / (1 - beta1^step), 1 / sqrt(1 - beta2^step)} (double) written.       */
+int unet_optim_prepare(const unet_optim_seg* segs, int nsegs, const unet_optim_group* groups, const double* partial,
+                       int nchunks, double max_norm, const float* grad_scale, const float* found_inf_in, double* bc,
+                       float* result, void* stream);
+/* torch.optim.AdamW.step (decoupled weight decay, amsgrad / maximize off; scripts/train.py:142, 156) on every
+ * ACTIVE ADAMW entry, with g' = result[2] * g:  p *= 1 - lr*wd;  m += (1-beta1)(g' - m);
+ * v = beta2*v + (1-beta2) g'^2;  p -= lr*bc1 * m / (sqrt(v)*bc2s + eps).  Writes nothing when result[1] != 0.  */
+int unet_optim_adamw(const unet_optim_seg* segs, const unet_optim_chunk* map, int nchunks,
+                     const unet_optim_group* groups, const double* bc, const float* result, void* stream);
+/* ModelEMA.update (unet/utils/general.py:156-184) in one launch: EMA entries p <- decay*p + one_minus_decay*g,
+ * COPY entries a byte copy (16 bytes wide where ALIGNED, with a byte-granular tail).                         */
+int unet_ema_update(const unet_optim_seg* segs, const unet_optim_chunk* map, int nchunks, float decay,
+                    float one_minus_decay, void* stream);
 
 #ifdef __cplusplus
 }

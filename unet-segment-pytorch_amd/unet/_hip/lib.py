@@ -73,6 +73,23 @@ class AugParams(ctypes.Structure):     # unet_aug_params (42 x 4 bytes; AUG_DTYP
 AUG_HFLIP, AUG_VFLIP, AUG_AFFINE, AUG_ELASTIC, AUG_GRID, AUG_BRIGHTNESS, AUG_NOISE, AUG_DROPOUT = (
     1, 2, 4, 8, 16, 32, 64, 128)
 
+class OptimSeg(ctypes.Structure):      # unet_optim_seg (56 bytes; np.dtype(OptimSeg) is the host table's row)
+    _fields_ = [("p", c_vp), ("g", c_vp), ("m", c_vp), ("v", c_vp), ("step", c_vp), ("numel", c_ll),
+                ("group", c_int), ("flags", c_int)]
+
+
+class OptimChunk(ctypes.Structure):    # unet_optim_chunk
+    _fields_ = [("seg", c_int), ("chunk", c_int)]
+
+
+class OptimGroup(ctypes.Structure):    # unet_optim_group
+    _fields_ = [("lr", ctypes.c_double), ("beta1", ctypes.c_double), ("beta2", ctypes.c_double),
+                ("eps", ctypes.c_double), ("weight_decay", ctypes.c_double), ("lr_ptr", c_vp)]
+
+
+OPTIM_CHUNK = 8192                     # UNET_OPTIM_CHUNK
+OPT_ACTIVE, OPT_ALIGNED, OPT_ADAMW, OPT_EMA, OPT_COPY = 1, 2, 0 << 4, 1 << 4, 2 << 4
+
 # name -> (restype, argtypes); mirrors include/unet_hip.h
 _SIGS = {
     "unet_last_error": (ctypes.c_char_p, []),
@@ -172,10 +189,15 @@ _SIGS = {
     "unet_aug_elastic_field": (c_int, [c_int, c_int, c_float, c_int, c_vp, c_ll, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "unet_aug_apply": (c_int, [c_ll, c_int, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_ll, c_vp, c_int, c_float,
                                c_float, c_vp, c_vp, c_vp]),
+    "unet_optim_chunks": (c_int, [c_ll]),
+    "unet_optim_gradnorm": (c_int, [c_vp, c_vp, c_int, c_vp, c_vp]),
+    "unet_optim_prepare": (c_int, [c_vp, c_int, c_vp, c_vp, c_int, ctypes.c_double, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "unet_optim_adamw": (c_int, [c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp]),
+    "unet_ema_update": (c_int, [c_vp, c_vp, c_int, c_float, c_float, c_vp]),
 }
 
 _lib = None
-ABI_VERSION = 113  # include/unet_hip.h UNET_ABI_VERSION
+ABI_VERSION = 114 # include/unet_hip.h UNET_ABI_VERSION
 
 # UNET_GUARD=1: bounds-checking debug mode (csrc/guard_alloc.cpp).  Every device allocation of the process
 # gets guard bands and every library call is bracketed by a device sync + a check of all bands, so an
@@ -187,7 +209,8 @@ _guard = None
 _NO_LAUNCH = {"unet_last_error", "unet_version", "unet_conv_mtiles", "unet_conv_stats_rows", "unet_conv_variant",
               "unet_wgrad_variant", "unet_conv_act_out_ok", "unet_conv_workspace", "unet_packed_weight_elems", "unet_wgrad_workspace",
               "unet_bn_bwd_reduce_rows", "unet_gate_psi_rows", "unet_gate_bwd2_rows", "unet_convt_bwd_rows",
-              "unet_outconv_rows", "unet_outconv_mc_ok", "unet_loss_rows", "unet_upsample_bwd_pw_ok", "unet_bn_bwd_pool_gate_ok"}
+              "unet_outconv_rows", "unet_outconv_mc_ok", "unet_loss_rows", "unet_upsample_bwd_pw_ok", "unet_bn_bwd_pool_gate_ok",
+              "unet_optim_chunks"}
 
 
 class HipLibraryError(RuntimeError):
