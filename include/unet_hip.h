@@ -29,8 +29,9 @@ extern "C" {
 /* unet_version() of a library built from this header.  110: unet_conv_desc gained `workspace` (round 5);
  * a caller built against an older header must not pass its (shorter) descriptors to this library.
  * 111: unet_aug_params, unet_aug_elastic_field and unet_aug_apply added (no existing layout changed)
- * 114: the optimizer tail (unet_optim_*, unet_ema_update) added (no existing layout changed) */
-#define UNET_ABI_VERSION 114
+ * 114: the optimizer tail (unet_optim_*, unet_ema_update) added (no existing layout changed)
+ * 115: the multi-class cross-entropy / Dice + CE loss (unet_ce_*) added (no existing layout changed) */
+#define UNET_ABI_VERSION 115
 
 enum { UNET_F32 = 0, UNET_BF16 = 1, UNET_F16 = 2 };  /* operand (activation / weight) type */
 enum { UNET_ERR_ARG = 1001, UNET_ERR_UNSUPPORTED = 1002 };
@@ -408,6 +409,44 @@ int unet_loss_finalize_multi(const float* partial, int rows, int S, const float*
 int unet_loss_grad_multi(int S, long long N, int K, long long HW, const float* const* z, const int64_t* t,
                          const float* coef, const float* gout, int gout_per_elem, int ignore_bg, float* const* dz,
                          void* stream);
+
+/* ---- weighted cross-entropy and Dice + CE for 2..16 classes (csrc/loss_ce.hip) -
+ * Logits fp32 NCHW (N, K, HW), targets int64 (N, HW), `weight` a device fp32 [K] or NULL (all ones).  A pixel is
+ * valid iff 0 <= t < K and t != ignore_index; every other label contributes to no sum and gets a zero gradient:
+ * unlike torch's nll_loss kernels, an out-of-range label never raises a device assert.  With
+ * nll_i = -w[t_i] logp_i[t_i], sm_i = -sum_k w[k] logp_i[k] and Wsum = sum_valid w[t_i]:
+ *   CE = ((1-eps) sum nll + (eps/K) sum sm) / Wsum  (reduction 0 'mean'; 1 'sum': no division; 2 'none': per pixel)
+ *   total = sum_s set_weights[s] * (ce_w * CE_s + dice_w * Dice_s),  Dice = the reference DiceLoss(mean) of
+ *   loss.py:18-85 with I_c, P_c, T_c taken over valid pixels (dice != 0 only).
+ * 2 <= K <= 16 and S <= 4 (else UNET_ERR_UNSUPPORTED).  No atomics: bit-identical from run to run.
+ * Each `_multi` form takes host arrays z / dz / set_weights of S same-shape sets with shared targets, as
+ * unet_loss_*_multi do (DeepSupervisionLoss, loss.py:194-229).                                              */
+/* pass 1, replaces F.log_softmax + F.nll_loss forward of torch.nn.CrossEntropyLoss (reference loss.py:253-256):
+ * partial [S][N][unet_loss_rows(HW)][F], F = 4 (sum w_t, sum nll, sum sm, #valid) + (dice ? 3K : 0) (I_c, P_c,
+ * T_c).  map: NULL, or (one set) the 'none' result (N, HW) = (1-eps) nll_i + (eps/K) sm_i, 0 where invalid.  */
+int unet_ce_reduce(long long N, int K, long long HW, const float* z, const int64_t* t, const float* weight,
+                   int ignore_index, double label_smoothing, int dice, float* partial, float* map, void* stream);
+int unet_ce_reduce_multi(int S, long long N, int K, long long HW, const float* const* z, const int64_t* t,
+                         const float* weight, int ignore_index, double label_smoothing, int dice, float* partial,
+                         float* map, void* stream);
+/* finalize, replaces the reductions and divisions of nll_loss / the label-smoothing branch of cross_entropy_loss:
+ * loss[0] = total (not written for 'none') and coef [S][4 + (dice ? 2NK : 0)] = {c_nll, c_sm, sum_k w_k, Wsum,
+ * gA[N][K], gB[N][K]}, c_nll = set_w ce_w (1-eps) / Wsum, c_sm = set_w ce_w (eps/K) / Wsum ('mean'; else no
+ * division).  'none' takes one set and no Dice term (UNET_ERR_ARG).                                         */
+int unet_ce_finalize(const float* partial, int rows, long long N, int K, const float* weight, float ce_w,
+                     float dice_w, double label_smoothing, float dice_smooth, int ignore_bg, int dice, int reduction,
+                     float* loss, float* coef, void* stream);
+int unet_ce_finalize_multi(const float* partial, int rows, int S, const float* set_weights, long long N, int K,
+                           const float* weight, float ce_w, float dice_w, double label_smoothing, float dice_smooth,
+                           int ignore_bg, int dice, int reduction, float* loss, float* coef, void* stream);
+/* pass 2, replaces nll_loss_backward + log_softmax_backward: dz = gout * d total / dz, gout a device scalar or
+ * (gout_per_pixel, one set) the upstream map (N, HW) of 'none'; zeros in all K planes of an invalid pixel.    */
+int unet_ce_grad(long long N, int K, long long HW, const float* z, const int64_t* t, const float* weight,
+                 int ignore_index, const float* coef, const float* gout, int gout_per_pixel, int dice, int ignore_bg,
+                 float* dz, void* stream);
+int unet_ce_grad_multi(int S, long long N, int K, long long HW, const float* const* z, const int64_t* t,
+                       const float* weight, int ignore_index, const float* coef, const float* gout,
+                       int gout_per_pixel, int dice, int ignore_bg, float* const* dz, void* stream);
 
 /* ---- device input pipeline and inference post-processing (csrc/infer.hip) ------------------- */
 /* One separable pass of PIL's 8-bit Image.resize(BILINEAR) (Resample.c) over a (N, inH, inW) uint8

@@ -194,10 +194,21 @@ _SIGS = {
     "unet_optim_prepare": (c_int, [c_vp, c_int, c_vp, c_vp, c_int, ctypes.c_double, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "unet_optim_adamw": (c_int, [c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp]),
     "unet_ema_update": (c_int, [c_vp, c_vp, c_int, c_float, c_float, c_vp]),
+    "unet_ce_reduce": (c_int, [c_ll, c_int, c_ll, c_vp, c_vp, c_vp, c_int, ctypes.c_double, c_int, c_vp, c_vp, c_vp]),
+    "unet_ce_reduce_multi": (c_int, [c_int, c_ll, c_int, c_ll, ctypes.POINTER(c_vp), c_vp, c_vp, c_int,
+                                     ctypes.c_double, c_int, c_vp, c_vp, c_vp]),
+    "unet_ce_finalize": (c_int, [c_vp, c_int, c_ll, c_int, c_vp, c_float, c_float, ctypes.c_double, c_float, c_int,
+                                 c_int, c_int, c_vp, c_vp, c_vp]),
+    "unet_ce_finalize_multi": (c_int, [c_vp, c_int, c_int, ctypes.POINTER(c_float), c_ll, c_int, c_vp, c_float,
+                                       c_float, ctypes.c_double, c_float, c_int, c_int, c_int, c_vp, c_vp, c_vp]),
+    "unet_ce_grad": (c_int, [c_ll, c_int, c_ll, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_int, c_int, c_vp,
+                             c_vp]),
+    "unet_ce_grad_multi": (c_int, [c_int, c_ll, c_int, c_ll, ctypes.POINTER(c_vp), c_vp, c_vp, c_int, c_vp, c_vp,
+                                   c_int, c_int, c_int, ctypes.POINTER(c_vp), c_vp]),
 }
 
 _lib = None
-ABI_VERSION = 114 # include/unet_hip.h UNET_ABI_VERSION
+ABI_VERSION = 115 # include/unet_hip.h UNET_ABI_VERSION
 
 # UNET_GUARD=1: bounds-checking debug mode (csrc/guard_alloc.cpp).  Every device allocation of the process
 # gets guard bands and every library call is bracketed by a device sync + a check of all bands, so an

@@ -2,12 +2,13 @@
 (confusion matrix counted on the device), the fused clip + AdamW step and ModelEMA (the tail of the
 training step).  The reference's host-side callbacks/plots/dataset are out of scope."""
 
-from .loss import DiceLoss, BalancedCELoss, DiceBCELoss, DeepSupervisionLoss, create_loss_function
+from .loss import (DiceLoss, BalancedCELoss, DiceBCELoss, CrossEntropyLoss, DiceCELoss, DeepSupervisionLoss,
+                   create_loss_function)
 from .metrics import SegmentationMetrics, compute_dice, compute_iou
 from .config import load_config, create_model, create_criterion, build_from_config, create_train_transform
 from .optim import FusedClipAdamW
 from .general import ModelEMA
 
-__all__ = ["FusedClipAdamW", "ModelEMA","DiceLoss", "BalancedCELoss", "DiceBCELoss", "DeepSupervisionLoss", "create_loss_function",
+__all__ = ["FusedClipAdamW", "ModelEMA","DiceLoss", "BalancedCELoss", "DiceBCELoss", "CrossEntropyLoss", "DiceCELoss", "DeepSupervisionLoss", "create_loss_function",
            "SegmentationMetrics", "compute_iou", "compute_dice", "load_config", "create_model", "create_criterion",
            "build_from_config", "create_train_transform"]

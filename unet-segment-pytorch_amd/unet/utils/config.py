@@ -6,7 +6,8 @@ Keys read (reference meaning unchanged):
   model.type (unet | attention_unet | attention), model.n_channels, model.n_classes, model.bilinear,
   model.base_features, model.deep_supervision;
   loss.type, loss.ce_weight, loss.dice_weight, loss.class_weights, loss.balanced_class_weight,
-  loss.ds_weights (deep supervision only);
+  loss.ds_weights (deep supervision only); loss.type also takes `dice_ce` (DiceCELoss: ce_weight, dice_weight and
+  class_weights, one weight per class);
   data.img_size and augmentation.enabled / horizontal_flip / rotation_limit / elastic / brightness_contrast
   (create_train_transform: the device form of the reference's training augmentation).
 Keys added:

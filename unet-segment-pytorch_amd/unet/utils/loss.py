@@ -3,6 +3,8 @@
 DiceLoss, BalancedCELoss and DiceBCELoss run as one fused HIP reduction + gradient pass
 (`unet_loss_*` in include/unet_hip.h): the reference's per-image Python loop with boolean-mask
 indexing (loss.py:134-145) becomes device-side per-image reductions, with no host sync.
+CrossEntropyLoss (the factory's 'ce') and DiceCELoss ('dice_ce') serve 2 to 16 classes with per-class weights,
+ignore_index and label smoothing through the `unet_ce_*` passes (csrc/loss_ce.hip).
 """
 
 from typing import Optional
@@ -91,6 +93,69 @@ class _FusedMultiLoss(torch.autograd.Function):
         return (None, None, None, *dz)
 
 
+class _FusedCE(torch.autograd.Function):
+    """Σ_s w_s · (ce_w · CE(z_s, t) + dice_w · Dice(z_s, t)) over S <= 4 same-shape logit sets: one reduce, one
+    finalize and one grad launch (`unet_ce_*`, csrc/loss_ce.hip; the `_multi` entry points when S > 1).
+    cfg = (ce_w, dice_w, ignore_index, label_smoothing, dice_smooth, ignore_bg, dice, reduction)."""
+
+    @staticmethod
+    def forward(ctx, t, weight, set_weights, cfg, *zs):
+        ce_w, dice_w, ignore_index, eps, dice_smooth, ignore_bg, dice, reduction = cfg
+        S = len(zs)
+        N, K, H, W = zs[0].shape
+        zc = [z.detach() if (z.dtype == torch.float32 and z.is_contiguous()) else z.detach().float().contiguous()
+              for z in zs]
+        tc = t if (t.dtype == torch.int64 and t.is_contiguous()) else t.long().contiguous()
+        wc = None if weight is None else weight.detach().float().contiguous()
+        HW, dev = H * W, zs[0].device
+        rows = L.load().unet_loss_rows(HW)
+        F = 4 + (3 * K if dice else 0)
+        part = f32(S, N, rows, F, device=dev)
+        coef = f32(S, 4 + (2 * N * K if dice else 0), device=dev)
+        loss = f32((), device=dev) if reduction != 2 else None
+        pmap = f32(N, H, W, device=dev) if reduction == 2 else None
+        fin = (N, K, vp(wc), ce_w, dice_w, eps, dice_smooth, int(ignore_bg), int(dice), reduction, vp(loss), vp(coef),
+               stream())
+        if S == 1:
+            L.call("unet_ce_reduce", N, K, HW, vp(zc[0]), vp(tc), vp(wc), ignore_index, eps, int(dice), vp(part),
+                   vp(pmap), stream())
+            L.call("unet_ce_finalize", vp(part), rows, *fin)
+        else:
+            zp = (L.c_vp * S)(*[z.data_ptr() for z in zc])
+            L.call("unet_ce_reduce_multi", S, N, K, HW, zp, vp(tc), vp(wc), ignore_index, eps, int(dice), vp(part),
+                   vp(pmap), stream())
+            L.call("unet_ce_finalize_multi", vp(part), rows, S, (L.c_float * S)(*set_weights), *fin)
+        ctx.save_for_backward(tc, coef, *([] if wc is None else [wc]), *zc)
+        ctx.cfg = (wc is not None, ignore_index, int(dice), int(ignore_bg), reduction)
+        return loss if reduction != 2 else pmap
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gout):
+        has_w, ignore_index, dice, ignore_bg, reduction = ctx.cfg
+        tc, coef, *rest = ctx.saved_tensors
+        wc, zc = (rest[0], rest[1:]) if has_w else (None, rest)
+        S = len(zc)
+        N, K, H, W = zc[0].shape
+        go = gout.float().contiguous()
+        dz = [torch.empty_like(z) for z in zc]
+        tail = (vp(coef), vp(go), int(reduction == 2), dice, ignore_bg)
+        if S == 1:
+            L.call("unet_ce_grad", N, K, H * W, vp(zc[0]), vp(tc), vp(wc), ignore_index, *tail, vp(dz[0]), stream())
+        else:
+            zp = (L.c_vp * S)(*[z.data_ptr() for z in zc])
+            dp = (L.c_vp * S)(*[d.data_ptr() for d in dz])
+            L.call("unet_ce_grad_multi", S, N, K, H * W, zp, vp(tc), vp(wc), ignore_index, *tail, dp, stream())
+        return (None, None, None, None, *dz)
+
+
+def _ce_hip_ok(z, t, weight) -> bool:
+    """whether (logits, class-index targets, weight buffer) is a case of the HIP cross-entropy"""
+    return (z.is_cuda and z.dim() == 4 and 2 <= z.shape[1] <= 16 and not t.is_floating_point()
+            and t.device == z.device and t.shape == (z.shape[0], z.shape[2], z.shape[3])
+            and (weight is None or (weight.device == z.device and weight.numel() == z.shape[1])))
+
+
 def _fused(z, t, ce_w, dice_w, class_w, ce_smooth=1e-6, dice_smooth=1.0, ignore_bg=True, reduction="mean"):
     require_device(z, "predictions")
     if z.dim() != 4 or t.shape != (z.shape[0], z.shape[2], z.shape[3]):
@@ -141,10 +206,55 @@ class DiceBCELoss(nn.Module):
                       self.balanced_ce.smooth, self.dice_loss.smooth, self.dice_loss.ignore_background, "mean")
 
 
+class CrossEntropyLoss(nn.CrossEntropyLoss):
+    """torch.nn.CrossEntropyLoss (same constructor, same `weight` buffer) whose (N, K, H, W) case with class-index
+    targets (N, H, W), 2 <= K <= 16, on a ROCm device runs as one fused HIP reduction + gradient pass
+    (csrc/loss_ce.hip).  There, a label outside [0, K) counts as ignored instead of raising a device assert.
+    Every other input (CPU tensors, probability targets, other ranks, other K) goes to torch's own forward."""
+
+    def forward(self, input: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+        if not _ce_hip_ok(input, target, self.weight):
+            return super().forward(input, target)
+        L.load(require_gpu=True)
+        cfg = (1.0, 0.0, int(self.ignore_index), float(self.label_smoothing), 1.0, False, False, _RED[self.reduction])
+        return _FusedCE.apply(target, self.weight, [1.0], cfg, input)
+
+
+class DiceCELoss(nn.Module):
+    """ce_weight * weighted CE(mean) + dice_weight * Dice(mean) for 2 to 16 classes, one fused pass of both terms:
+    the cross-entropy weights every class (`class_weights`), and both terms leave out the pixels labelled
+    `ignore_index` or outside [0, K)."""
+
+    def __init__(self, ce_weight: float = 1.0, dice_weight: float = 1.0, class_weights: Optional[list] = None,
+                 ignore_index: int = -100, label_smoothing: float = 0.0, smooth: float = 1.0,
+                 ignore_background: bool = True):
+        super().__init__()
+        self.ce_weight = ce_weight
+        self.dice_weight = dice_weight
+        self.register_buffer("weight", None if class_weights is None
+                             else torch.as_tensor(class_weights, dtype=torch.float32))
+        self.ignore_index = ignore_index
+        self.label_smoothing = label_smoothing
+        self.smooth = smooth
+        self.ignore_background = ignore_background
+
+    def _cfg(self):
+        return (float(self.ce_weight), float(self.dice_weight), int(self.ignore_index), float(self.label_smoothing),
+                float(self.smooth), bool(self.ignore_background), True, 0)
+
+    def forward(self, predictions: torch.Tensor, targets: torch.Tensor) -> torch.Tensor:
+        require_device(predictions, "predictions")
+        if not _ce_hip_ok(predictions, targets, self.weight):
+            raise RuntimeError(f"DiceCELoss expects predictions (N, 2..16, H, W), class-index targets (N, H, W) and its "
+                               f"weights on one device; got {tuple(predictions.shape)} and {tuple(targets.shape)}")
+        return _FusedCE.apply(targets, self.weight, [1.0], self._cfg(), predictions)
+
+
 class DeepSupervisionLoss(nn.Module):
     """Σ_k w_k · base(pred_k, targets) over [main, ds1, ds2, ds3] — reference loss.py:194-229.
-    With one of the fused bases (DiceBCE / Dice(mean) / BalancedCE) all the sets run through one launch of
-    each loss pass; any other base criterion is applied per set as in the reference."""
+    With one of the fused bases (DiceBCE / Dice(mean) / BalancedCE, or CrossEntropyLoss(mean | sum) / DiceCELoss)
+    all the sets run through one launch of each loss pass; any other base criterion is applied per set as in the
+    reference."""
 
     def __init__(self, base_criterion: nn.Module, weights: list = None):
         super().__init__()
@@ -155,8 +265,14 @@ class DeepSupervisionLoss(nn.Module):
         if isinstance(predictions, (list, tuple)):
             cfg = _fused_cfg(self.base_criterion)
             n = min(len(predictions), len(self.weights))
-            if (cfg is not None and 1 <= n <= 4 and all(p.dim() == 4 and p.shape == predictions[0].shape
-                                                        for p in predictions[:n])):
+            same = 1 <= n <= 4 and all(p.dim() == 4 and p.shape == predictions[0].shape for p in predictions[:n])
+            ce_cfg = _ce_cfg(self.base_criterion)
+            if ce_cfg is not None and same and _ce_hip_ok(predictions[0], targets, self.base_criterion.weight):
+                # likewise through unet_ce_*_multi
+                L.load(require_gpu=True)
+                return _FusedCE.apply(targets, self.base_criterion.weight, [float(w) for w in self.weights[:n]],
+                                      ce_cfg, *predictions[:n])
+            if cfg is not None and same:
                 # the four logit sets through one reduce / finalize / grad launch (unet_loss_*_multi)
                 require_device(predictions[0], "predictions")
                 if targets.shape != (predictions[0].shape[0], predictions[0].shape[2], predictions[0].shape[3]):
@@ -182,17 +298,29 @@ def _fused_cfg(crit: nn.Module):
     return None
 
 
+def _ce_cfg(crit: nn.Module):
+    """the _FusedCE configuration of a CrossEntropyLoss (mean or sum) or DiceCELoss base, else None"""
+    if type(crit) is CrossEntropyLoss and crit.reduction in ("mean", "sum"):
+        return (1.0, 0.0, int(crit.ignore_index), float(crit.label_smoothing), 1.0, False, False, _RED[crit.reduction])
+    if type(crit) is DiceCELoss:
+        return crit._cfg()
+    return None
+
+
 def create_loss_function(loss_type: str = "dice_bce", ce_weight: float = 1.0, dice_weight: float = 1.0,
                          class_weights: Optional[list] = None, balanced_class_weight: float = 0.5,
                          **kwargs) -> nn.Module:
-    """Factory — reference loss.py:232-271 ('dice' | 'ce'/'crossentropy' | 'balanced_ce' | 'dice_bce')."""
+    """Factory — reference loss.py:232-271 ('dice' | 'ce'/'crossentropy' | 'balanced_ce' | 'dice_bce'), and
+    'dice_ce': DiceCELoss(ce_weight, dice_weight, class_weights)."""
     kind = loss_type.lower()
     if kind == "dice":
         return DiceLoss(ignore_background=True)
     if kind in ("ce", "crossentropy"):
         if class_weights is not None:
-            return nn.CrossEntropyLoss(weight=torch.tensor(class_weights, dtype=torch.float32))
-        return nn.CrossEntropyLoss()
+            return CrossEntropyLoss(weight=torch.tensor(class_weights, dtype=torch.float32))
+        return CrossEntropyLoss()
+    if kind == "dice_ce":
+        return DiceCELoss(ce_weight=ce_weight, dice_weight=dice_weight, class_weights=class_weights)
     if kind == "balanced_ce":
         return BalancedCELoss(class_weight=balanced_class_weight)
     if kind == "dice_bce":
