@@ -1,5 +1,6 @@
-"""fp64 references of the streaming kernels around the convolutions (csrc/bn.hip, csrc/gate.hip, csrc/loss.hip and
-csrc/misc.hip: OutConv, resampling, the ConvTranspose2d backward prep, max-pool, materialised sources, layouts),
+"""fp64 references of the streaming kernels around the convolutions (csrc/bn.hip, csrc/gate.hip, csrc/loss.hip,
+csrc/outconv.hip, csrc/upsample_bwd.hip: resampling, and csrc/layout.hip: the ConvTranspose2d backward prep, max-pool,
+materialised sources, layouts),
 written from the maths of nn.BatchNorm2d, ReLU, AttentionGate (layers.py:126-192), the Dice / balanced
 cross-entropy losses (loss.py:18-229), bilinear interpolation and MaxPool2d, not from the kernels.  Pure torch; every
 function takes the kernels' own operands (any dtype, any device), evaluates in float64 and returns what the matching
@@ -338,7 +339,7 @@ def loss_dz_terms(z, t, coef, gout, per_elem, ignore_bg):
     return NS(dz=dz, abs_terms=terms)
 
 
-# ---- bilinear resampling, align_corners=True (csrc/misc.hip) ----------------------------------------
+# ---- bilinear resampling, align_corners=True (csrc/upsample_bwd.hip) ----------------------------------------
 
 def resize(x, Ho, Wo):
     """x [..., Hi, Wi] (NCHW) -> [..., Ho, Wo]"""

@@ -1,4 +1,4 @@
-"""GPU op-level numerics of the pooling, materialise, layout and fill kernels of csrc/misc.hip —
+"""GPU op-level numerics of the pooling, materialise, layout and fill kernels of csrc/layout.hip —
 unet_materialize_pool, unet_materialize (all source kinds, the vector fast path, the generic kernel and its channel
 tail), unet_nchw_to_nhwc, unet_nhwc_to_nchw, unet_gated_to_nchw and unet_fill_f32 — against the fp64 references of
 tests/ref_ops.py (proved against nn.functional in tests/test_ref_ops_cpu.py).  Outputs are NaN-filled before the

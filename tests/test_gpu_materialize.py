@@ -1,4 +1,4 @@
-"""Op test of `unet_materialize` (csrc/misc.hip: the LDS-tiled Up-block kernel since round 5 for 16-bit maps, the
+"""Op test of `unet_materialize` (csrc/layout.hip: the LDS-tiled Up-block kernel since round 5 for 16-bit maps, the
 packed-fp32 per-element kernel otherwise and under UNET_MAT_TILE=0): the
 bilinear x2 upsample (align_corners=True) of relu?(y * scale + shift), placed with the skip-size padding —
 the decoder input of every Up block (reference unet/models/layers.py:78,183 `nn.Upsample(scale_factor=2,

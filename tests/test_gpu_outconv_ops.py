@@ -1,4 +1,4 @@
-"""GPU op-level numerics of OutConv (1x1 conv + bias over a BN + ReLU source, csrc/misc.hip): the forward, the
+"""GPU op-level numerics of OutConv (1x1 conv + bias over a BN + ReLU source, csrc/outconv.hip): the forward, the
 backward and the backward fused with the BatchNorm backward of its input, through the C-ABI, against the fp64
 references of tests/ref_ops.py.  Output buffers are filled with NaN (or a known value where the call accumulates)
 before the launch and must come back finite.  The ReLU masks are exact: the kernels evaluate the pre-activation as

@@ -1,4 +1,4 @@
-"""GPU op-level numerics of the resampling kernels of csrc/misc.hip — unet_resize_nchw / unet_resize_nchw_bwd (the
+"""GPU op-level numerics of the resampling kernels of csrc/upsample_bwd.hip — unet_resize_nchw / unet_resize_nchw_bwd (the
 deep-supervision heads), unet_upsample_bwd (all four kernels, each case asserted to reach the kernel it is meant
 for) and unet_convt_bwd_prep — against the fp64 references of tests/ref_ops.py (F.interpolate, autograd and a
 selection; proved against dense tap matrices, pixel_unshuffle and ConvTranspose2d's autograd in
@@ -110,7 +110,7 @@ UPB_J, UPB_VMAX = 16, 56
 
 
 def _upb_kernel(C, up_h, up_w, sh, sw, tile_env=True):
-    """the kernel unet_upsample_bwd launches (csrc/misc.hip): the window test in fp32, as the host forms it"""
+    """the kernel unet_upsample_bwd launches (csrc/upsample_bwd.hip): the window test in fp32, as the host forms it"""
     def span(sc, up):
         return int(math.floor(np.float32(2.0) / np.float32(sc))) + 3 if sc > 0 else up + 8
     if C % 4:

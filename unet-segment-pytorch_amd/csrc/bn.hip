@@ -150,12 +150,7 @@ __global__ void bn_eval_kernel(int C, const float* gamma, const float* beta, con
   if (invstd) invstd[c] = is;
 }
 
-// 2-D layout: CL channel lanes x (256/CL) pixel rows; grid (ceil(C/CL), rows)
-static inline int chan_lanes(int C) {
-  int cl = 1;
-  while (cl < C && cl < 64) cl <<= 1;
-  return cl;
-}
+// 2-D layout: CL = chan_lanes(C) channel lanes x (256/CL) pixel rows; grid (ceil(C/CL), rows)
 static inline int reduce_rows(long long P, int C) {
   const int cl = chan_lanes(C);
   const int cblocks = (C + cl - 1) / cl;
@@ -401,7 +396,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_vec_kernel(long long P, int 
         const float gj = (relu && !(__builtin_fmaf(yv[u][j], sc[j], sf[j]) > 0.f)) ? 0.f : g[u][j];
         // explicit fma order, here and in the pre-activation y * scale + shift of the ReLU masks (the compiler's
         // contraction choice moved with the code's shape in round 6: fused and unfused paths must round alike);
-        // the OutConv and attention-gate forms (misc.hip, gate.hip) round the same way
+        // the OutConv and attention-gate forms (outconv.hip, gate.hip) round the same way
         o[j] = f32_rounded(__builtin_fmaf(A[j], gj, __builtin_fmaf(B[j], yv[u][j], Cc[j])));
       }
       if constexpr (sizeof(T) == 2) {
@@ -536,6 +531,48 @@ __global__ void colsum_kernel(const float* part, int rows, int C, float* out, in
   if (threadIdx.x == 0) out[c] = accum ? out[c] + (float)a : (float)a;
 }
 
+// T from y's dtype code, as UNET_DISPATCH_T; G, the gradient's type: float for an fp32 da, T otherwise (the entry
+// points admit a 16-bit da only beside y of the same type), so <T, float> and <T, T> are all that is instantiated
+#define BN_DISPATCH_TG(code, da_code, ...)                                                          \
+  UNET_DISPATCH_T(code, (da_code) == UNET_F32 ? [&]() { using G = float; return __VA_ARGS__; }() \
+                                              : [&]() { using G = T; return __VA_ARGS__; }())
+
+template <typename T, typename G, bool POOL>
+static int launch_bn_bwd_reduce_vec(const char* what, hipStream_t st, long long P, int C, const void* da, const void* y,
+                                    const float* scale, const float* shift, int relu, const float* mean,
+                                    const float* invstd, float* partial, const PoolG& pg) {
+  const int rows = reduce_rows_vec(P, C);
+  hipLaunchKernelGGL((bn_bwd_reduce_vec_kernel<T, G, POOL>), dim3(rows), dim3(256), 0, st, P, C, (const G*)da,
+                     (const T*)y, scale, shift, relu, mean, invstd, partial, rows, pg);
+  return check_launch(what);
+}
+template <typename T, typename G>
+static int launch_bn_bwd_reduce(hipStream_t st, long long P, int C, const void* da, const void* y, const float* scale,
+                                const float* shift, int relu, const float* mean, const float* invstd, float* partial) {
+  const int cl = chan_lanes(C), rows = reduce_rows(P, C);
+  hipLaunchKernelGGL((bn_bwd_reduce_kernel<T, G>), dim3(cdiv(C, cl), rows), dim3(256), 0, st, P, C, cl, (const G*)da,
+                     (const T*)y, scale, shift, relu, mean, invstd, partial, rows);
+  return check_launch("bn_bwd_reduce");
+}
+template <typename T, typename G, bool POOL>
+static int launch_bn_bwd_apply_vec(const char* what, hipStream_t st, long long P, int C, const void* da, const void* y,
+                                   const float* scale, const float* shift, int relu, const float* coef, void* dy,
+                                   const PoolG& pg) {
+  long long b = (P * (C / 8) + 255) / 256;
+  if (b > 8192) b = 8192;
+  hipLaunchKernelGGL((bn_bwd_apply_vec_kernel<T, G, POOL>), dim3((int)b), dim3(256), 0, st, P, C, (const G*)da,
+                     (const T*)y, scale, shift, relu, coef, (T*)dy, pg);
+  return check_launch(what);
+}
+template <typename T, typename G>
+static int launch_bn_bwd_apply(hipStream_t st, long long P, int C, const void* da, const void* y, const float* scale,
+                               const float* shift, int relu, const float* coef, void* dy) {
+  const int cl = chan_lanes(C), rows = reduce_rows(P, C);
+  hipLaunchKernelGGL((bn_bwd_apply_kernel<T, G>), dim3(cdiv(C, cl), rows), dim3(256), 0, st, P, C, cl, (const G*)da,
+                     (const T*)y, scale, shift, relu, coef, (T*)dy, rows);
+  return check_launch("bn_bwd_apply");
+}
+
 }  // namespace unet
 
 using namespace unet;
@@ -640,43 +677,10 @@ int unet_bn_bwd_reduce(int dtype, int da_dtype, long long P, int C, const void* 
                        void* stream) {
   hipStream_t st = (hipStream_t)stream;
   if (da_dtype != UNET_F32 && da_dtype != dtype) { set_error("unet_bn_bwd_reduce: a 16-bit gradient needs y of the same type"); return UNET_ERR_ARG; }
-  if (bn_vec_ok(C)) {
-    const int rows = reduce_rows_vec(P, C);
-    if (dtype == UNET_F16 && da_dtype == UNET_F16)
-      hipLaunchKernelGGL((bn_bwd_reduce_vec_kernel<f16, f16>), dim3(rows), dim3(256), 0, st, P, C, (const f16*)da,
-                         (const f16*)y, scale, shift, relu, mean, invstd, partial, rows);
-    else if (dtype == UNET_BF16 && da_dtype == UNET_BF16)
-      hipLaunchKernelGGL((bn_bwd_reduce_vec_kernel<bf16, bf16>), dim3(rows), dim3(256), 0, st, P, C, (const bf16*)da,
-                         (const bf16*)y, scale, shift, relu, mean, invstd, partial, rows);
-    else if (dtype == UNET_F16)
-      hipLaunchKernelGGL((bn_bwd_reduce_vec_kernel<f16, float>), dim3(rows), dim3(256), 0, st, P, C, (const float*)da,
-                         (const f16*)y, scale, shift, relu, mean, invstd, partial, rows);
-    else if (dtype == UNET_BF16)
-      hipLaunchKernelGGL((bn_bwd_reduce_vec_kernel<bf16, float>), dim3(rows), dim3(256), 0, st, P, C, (const float*)da,
-                         (const bf16*)y, scale, shift, relu, mean, invstd, partial, rows);
-    else
-      hipLaunchKernelGGL((bn_bwd_reduce_vec_kernel<float, float>), dim3(rows), dim3(256), 0, st, P, C, (const float*)da,
-                         (const float*)y, scale, shift, relu, mean, invstd, partial, rows);
-    return check_launch("bn_bwd_reduce");
-  }
-  const int cl = chan_lanes(C), rows = reduce_rows(P, C);
-  dim3 grid(cdiv(C, cl), rows);
-  if (dtype == UNET_F16 && da_dtype == UNET_F16)
-    hipLaunchKernelGGL((bn_bwd_reduce_kernel<f16, f16>), grid, dim3(256), 0, st, P, C, cl, (const f16*)da,
-                       (const f16*)y, scale, shift, relu, mean, invstd, partial, rows);
-  else if (dtype == UNET_BF16 && da_dtype == UNET_BF16)
-    hipLaunchKernelGGL((bn_bwd_reduce_kernel<bf16, bf16>), grid, dim3(256), 0, st, P, C, cl, (const bf16*)da,
-                       (const bf16*)y, scale, shift, relu, mean, invstd, partial, rows);
-  else if (dtype == UNET_F16)
-    hipLaunchKernelGGL((bn_bwd_reduce_kernel<f16, float>), grid, dim3(256), 0, st, P, C, cl, (const float*)da,
-                       (const f16*)y, scale, shift, relu, mean, invstd, partial, rows);
-  else if (dtype == UNET_BF16)
-    hipLaunchKernelGGL((bn_bwd_reduce_kernel<bf16, float>), grid, dim3(256), 0, st, P, C, cl, (const float*)da,
-                       (const bf16*)y, scale, shift, relu, mean, invstd, partial, rows);
-  else
-    hipLaunchKernelGGL((bn_bwd_reduce_kernel<float, float>), grid, dim3(256), 0, st, P, C, cl, (const float*)da,
-                       (const float*)y, scale, shift, relu, mean, invstd, partial, rows);
-  return check_launch("bn_bwd_reduce");
+  if (bn_vec_ok(C))
+    return BN_DISPATCH_TG(dtype, da_dtype, launch_bn_bwd_reduce_vec<T, G, false>("bn_bwd_reduce", st, P, C, da, y, scale, shift,
+                                                                                 relu, mean, invstd, partial, PoolG{}));
+  return BN_DISPATCH_TG(dtype, da_dtype, launch_bn_bwd_reduce<T, G>(st, P, C, da, y, scale, shift, relu, mean, invstd, partial));
 }
 
 int unet_bn_bwd_finalize(const float* sum_g, const float* sum_gx, int rows, int C, long long count, const float* gamma,
@@ -695,44 +699,10 @@ int unet_bn_bwd_apply(int dtype, int da_dtype, long long P, int C, const void* d
                       const float* shift, int relu, const float* coef, void* dy, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   if (da_dtype != UNET_F32 && da_dtype != dtype) { set_error("unet_bn_bwd_apply: a 16-bit gradient needs y of the same type"); return UNET_ERR_ARG; }
-  if (bn_vec_ok(C)) {
-    long long b = (P * (C / 8) + 255) / 256;
-    if (b > 8192) b = 8192;
-    if (dtype == UNET_F16 && da_dtype == UNET_F16)
-      hipLaunchKernelGGL((bn_bwd_apply_vec_kernel<f16, f16>), dim3((int)b), dim3(256), 0, st, P, C, (const f16*)da,
-                         (const f16*)y, scale, shift, relu, coef, (f16*)dy);
-    else if (dtype == UNET_BF16 && da_dtype == UNET_BF16)
-      hipLaunchKernelGGL((bn_bwd_apply_vec_kernel<bf16, bf16>), dim3((int)b), dim3(256), 0, st, P, C, (const bf16*)da,
-                         (const bf16*)y, scale, shift, relu, coef, (bf16*)dy);
-    else if (dtype == UNET_F16)
-      hipLaunchKernelGGL((bn_bwd_apply_vec_kernel<f16, float>), dim3((int)b), dim3(256), 0, st, P, C, (const float*)da,
-                         (const f16*)y, scale, shift, relu, coef, (f16*)dy);
-    else if (dtype == UNET_BF16)
-      hipLaunchKernelGGL((bn_bwd_apply_vec_kernel<bf16, float>), dim3((int)b), dim3(256), 0, st, P, C, (const float*)da,
-                         (const bf16*)y, scale, shift, relu, coef, (bf16*)dy);
-    else
-      hipLaunchKernelGGL((bn_bwd_apply_vec_kernel<float, float>), dim3((int)b), dim3(256), 0, st, P, C, (const float*)da,
-                         (const float*)y, scale, shift, relu, coef, (float*)dy);
-    return check_launch("bn_bwd_apply");
-  }
-  const int cl = chan_lanes(C), rows = reduce_rows(P, C);
-  dim3 grid(cdiv(C, cl), rows);
-  if (dtype == UNET_F16 && da_dtype == UNET_F16)
-    hipLaunchKernelGGL((bn_bwd_apply_kernel<f16, f16>), grid, dim3(256), 0, st, P, C, cl, (const f16*)da,
-                       (const f16*)y, scale, shift, relu, coef, (f16*)dy, rows);
-  else if (dtype == UNET_BF16 && da_dtype == UNET_BF16)
-    hipLaunchKernelGGL((bn_bwd_apply_kernel<bf16, bf16>), grid, dim3(256), 0, st, P, C, cl, (const bf16*)da,
-                       (const bf16*)y, scale, shift, relu, coef, (bf16*)dy, rows);
-  else if (dtype == UNET_F16)
-    hipLaunchKernelGGL((bn_bwd_apply_kernel<f16, float>), grid, dim3(256), 0, st, P, C, cl, (const float*)da,
-                       (const f16*)y, scale, shift, relu, coef, (f16*)dy, rows);
-  else if (dtype == UNET_BF16)
-    hipLaunchKernelGGL((bn_bwd_apply_kernel<bf16, float>), grid, dim3(256), 0, st, P, C, cl, (const float*)da,
-                       (const bf16*)y, scale, shift, relu, coef, (bf16*)dy, rows);
-  else
-    hipLaunchKernelGGL((bn_bwd_apply_kernel<float, float>), grid, dim3(256), 0, st, P, C, cl, (const float*)da,
-                       (const float*)y, scale, shift, relu, coef, (float*)dy, rows);
-  return check_launch("bn_bwd_apply");
+  if (bn_vec_ok(C))
+    return BN_DISPATCH_TG(dtype, da_dtype, launch_bn_bwd_apply_vec<T, G, false>("bn_bwd_apply", st, P, C, da, y, scale, shift,
+                                                                                relu, coef, dy, PoolG{}));
+  return BN_DISPATCH_TG(dtype, da_dtype, launch_bn_bwd_apply<T, G>(st, P, C, da, y, scale, shift, relu, coef, dy));
 }
 
 // BN backward of a Down block's input activation with the pooled gradient folded in (PoolG above)
@@ -740,7 +710,6 @@ int unet_bn_bwd_reduce_pool(int dtype, long long N, int H, int W, int C, const f
                             const uint8_t* code, int ph, int pw, const void* y, const float* scale,
                             const float* shift, int relu, const float* mean, const float* invstd, float* partial,
                             void* stream) {
-  hipStream_t st = (hipStream_t)stream;
   const long long P = N * H * W;
   if (!bn_vec_ok(C) || !g2 || !code || P <= 0 || P >= (1LL << 31) || ph > (H >> 1) || pw > (W >> 1) || ph < 0 ||
       pw < 0) {
@@ -748,23 +717,13 @@ int unet_bn_bwd_reduce_pool(int dtype, long long N, int H, int W, int C, const f
     return UNET_ERR_ARG;
   }
   const PoolG pg{g2, code, H, W, ph, pw};
-  const int rows = reduce_rows_vec(P, C);
-  if (dtype == UNET_F16)
-    hipLaunchKernelGGL((bn_bwd_reduce_vec_kernel<f16, float, true>), dim3(rows), dim3(256), 0, st, P, C, da,
-                       (const f16*)y, scale, shift, relu, mean, invstd, partial, rows, pg);
-  else if (dtype == UNET_BF16)
-    hipLaunchKernelGGL((bn_bwd_reduce_vec_kernel<bf16, float, true>), dim3(rows), dim3(256), 0, st, P, C, da,
-                       (const bf16*)y, scale, shift, relu, mean, invstd, partial, rows, pg);
-  else
-    hipLaunchKernelGGL((bn_bwd_reduce_vec_kernel<float, float, true>), dim3(rows), dim3(256), 0, st, P, C, da,
-                       (const float*)y, scale, shift, relu, mean, invstd, partial, rows, pg);
-  return check_launch("bn_bwd_reduce_pool");
+  return UNET_DISPATCH_T(dtype, launch_bn_bwd_reduce_vec<T, float, true>("bn_bwd_reduce_pool", (hipStream_t)stream, P, C, da,
+                                                                         y, scale, shift, relu, mean, invstd, partial, pg));
 }
 
 int unet_bn_bwd_apply_pool(int dtype, long long N, int H, int W, int C, const float* da, const float* g2,
                            const uint8_t* code, int ph, int pw, const void* y, const float* scale, const float* shift,
                            int relu, const float* coef, void* dy, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
   const long long P = N * H * W;
   if (!bn_vec_ok(C) || !g2 || !code || P <= 0 || P >= (1LL << 31) || ph > (H >> 1) || pw > (W >> 1) || ph < 0 ||
       pw < 0) {
@@ -772,18 +731,8 @@ int unet_bn_bwd_apply_pool(int dtype, long long N, int H, int W, int C, const fl
     return UNET_ERR_ARG;
   }
   const PoolG pg{g2, code, H, W, ph, pw};
-  long long b = (P * (C / 8) + 255) / 256;
-  if (b > 8192) b = 8192;
-  if (dtype == UNET_F16)
-    hipLaunchKernelGGL((bn_bwd_apply_vec_kernel<f16, float, true>), dim3((int)b), dim3(256), 0, st, P, C, da,
-                       (const f16*)y, scale, shift, relu, coef, (f16*)dy, pg);
-  else if (dtype == UNET_BF16)
-    hipLaunchKernelGGL((bn_bwd_apply_vec_kernel<bf16, float, true>), dim3((int)b), dim3(256), 0, st, P, C, da,
-                       (const bf16*)y, scale, shift, relu, coef, (bf16*)dy, pg);
-  else
-    hipLaunchKernelGGL((bn_bwd_apply_vec_kernel<float, float, true>), dim3((int)b), dim3(256), 0, st, P, C, da,
-                       (const float*)y, scale, shift, relu, coef, (float*)dy, pg);
-  return check_launch("bn_bwd_apply_pool");
+  return UNET_DISPATCH_T(dtype, launch_bn_bwd_apply_vec<T, float, true>("bn_bwd_apply_pool", (hipStream_t)stream, P, C, da, y,
+                                                                        scale, shift, relu, coef, dy, pg));
 }
 
 int unet_colsum(const float* part, int rows, int C, float* out, int accum, void* stream) {

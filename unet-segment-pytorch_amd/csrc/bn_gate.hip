@@ -269,6 +269,35 @@ static bool gate_bn_shape_ok(int dtype, long long N, int H, int W, int C, int Ci
   return (C == 64 || C == 128) && (Ci == 32 || Ci == 64);
 }
 
+// one launcher per pass, T by UNET_DISPATCH_T16; NCH = Ci / 32 chunks of projection channels (1 or 2: gate_bn_shape_ok)
+template <typename T>
+static int launch_reduce_pool_gate(int Ci, hipStream_t st, long long P, int C, const GateBnArgs& a, const void* y,
+                                   const float* scale, const float* shift, int relu, const float* mean,
+                                   const float* invstd, float* partial) {
+  const int rows = unet_bn_bwd_reduce_rows(P, C);
+  if (Ci == 32)
+    hipLaunchKernelGGL((bn_bwd_reduce_pool_gate_kernel<T, 1>), dim3(rows), dim3(256), 0, st, P, C, a, (const T*)y, scale,
+                       shift, relu, mean, invstd, partial, rows);
+  else
+    hipLaunchKernelGGL((bn_bwd_reduce_pool_gate_kernel<T, 2>), dim3(rows), dim3(256), 0, st, P, C, a, (const T*)y, scale,
+                       shift, relu, mean, invstd, partial, rows);
+  return check_launch("bn_bwd_reduce_pool_gate");
+}
+template <typename T>
+static int launch_apply_pool_gate(int Ci, hipStream_t st, long long P, int C, const GateBnArgs& a, const void* y,
+                                  const float* scale, const float* shift, int relu, const float* coef, void* dy) {
+  // one (tile, channel group) item per wave: 512 elements, as a thread of bn_bwd_apply_vec_kernel owns 8
+  long long b = ((P + 15) / 16 * (C / 32) + 3) / 4;
+  if (b > 8192) b = 8192;
+  if (Ci == 32)
+    hipLaunchKernelGGL((bn_bwd_apply_pool_gate_kernel<T, 1>), dim3((int)b), dim3(256), 0, st, P, C, a, (const T*)y, scale,
+                       shift, relu, coef, (T*)dy);
+  else
+    hipLaunchKernelGGL((bn_bwd_apply_pool_gate_kernel<T, 2>), dim3((int)b), dim3(256), 0, st, P, C, a, (const T*)y, scale,
+                       shift, relu, coef, (T*)dy);
+  return check_launch("bn_bwd_apply_pool_gate");
+}
+
 }  // namespace unet
 
 using namespace unet;
@@ -284,7 +313,6 @@ int unet_bn_bwd_reduce_pool_gate(int dtype, long long N, int H, int W, int C, in
                                  const float* g2, const uint8_t* code, int ph, int pw, const void* y,
                                  const float* scale, const float* shift, int relu, const float* mean,
                                  const float* invstd, float* partial, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
   if (!gate_bn_shape_ok(dtype, N, H, W, C, Ci, ph, pw) || !dxs || !dxw || !wt_packed || !gate_p || !gate_ab || !g2 ||
       !code || !y || !partial) {
     set_error("unet_bn_bwd_reduce_pool_gate: bad arguments (16-bit, C 64 / 128, Ci 32 / 64)");
@@ -292,23 +320,8 @@ int unet_bn_bwd_reduce_pool_gate(int dtype, long long N, int H, int W, int C, in
   }
   const long long P = N * H * W;
   const GateBnArgs a{dxs, dxw, wt_packed, gate_p, gate_ab, g2, code, H, W, ph, pw};
-  const int rows = unet_bn_bwd_reduce_rows(P, C);
-  if (dtype == UNET_F16) {
-    if (Ci == 32)
-      hipLaunchKernelGGL((bn_bwd_reduce_pool_gate_kernel<f16, 1>), dim3(rows), dim3(256), 0, st, P, C, a, (const f16*)y,
-                         scale, shift, relu, mean, invstd, partial, rows);
-    else
-      hipLaunchKernelGGL((bn_bwd_reduce_pool_gate_kernel<f16, 2>), dim3(rows), dim3(256), 0, st, P, C, a, (const f16*)y,
-                         scale, shift, relu, mean, invstd, partial, rows);
-  } else {
-    if (Ci == 32)
-      hipLaunchKernelGGL((bn_bwd_reduce_pool_gate_kernel<bf16, 1>), dim3(rows), dim3(256), 0, st, P, C, a,
-                         (const bf16*)y, scale, shift, relu, mean, invstd, partial, rows);
-    else
-      hipLaunchKernelGGL((bn_bwd_reduce_pool_gate_kernel<bf16, 2>), dim3(rows), dim3(256), 0, st, P, C, a,
-                         (const bf16*)y, scale, shift, relu, mean, invstd, partial, rows);
-  }
-  return check_launch("bn_bwd_reduce_pool_gate");
+  return UNET_DISPATCH_T16(dtype, launch_reduce_pool_gate<T>(Ci, (hipStream_t)stream, P, C, a, y, scale, shift, relu, mean,
+                                                             invstd, partial));
 }
 
 int unet_bn_bwd_apply_pool_gate(int dtype, long long N, int H, int W, int C, int Ci, const float* dxs,
@@ -316,7 +329,6 @@ int unet_bn_bwd_apply_pool_gate(int dtype, long long N, int H, int W, int C, int
                                 const float* g2, const uint8_t* code, int ph, int pw, const void* y,
                                 const float* scale, const float* shift, int relu, const float* coef, void* dy,
                                 void* stream) {
-  hipStream_t st = (hipStream_t)stream;
   if (!gate_bn_shape_ok(dtype, N, H, W, C, Ci, ph, pw) || !dxs || !dxw || !wt_packed || !gate_p || !gate_ab || !g2 ||
       !code || !y || !coef || !dy) {
     set_error("unet_bn_bwd_apply_pool_gate: bad arguments (16-bit, C 64 / 128, Ci 32 / 64)");
@@ -324,25 +336,8 @@ int unet_bn_bwd_apply_pool_gate(int dtype, long long N, int H, int W, int C, int
   }
   const long long P = N * H * W;
   const GateBnArgs a{dxs, dxw, wt_packed, gate_p, gate_ab, g2, code, H, W, ph, pw};
-  // one (tile, channel group) item per wave: 512 elements, as a thread of bn_bwd_apply_vec_kernel owns 8
-  long long b = ((P + 15) / 16 * (C / 32) + 3) / 4;
-  if (b > 8192) b = 8192;
-  if (dtype == UNET_F16) {
-    if (Ci == 32)
-      hipLaunchKernelGGL((bn_bwd_apply_pool_gate_kernel<f16, 1>), dim3((int)b), dim3(256), 0, st, P, C, a, (const f16*)y,
-                         scale, shift, relu, coef, (f16*)dy);
-    else
-      hipLaunchKernelGGL((bn_bwd_apply_pool_gate_kernel<f16, 2>), dim3((int)b), dim3(256), 0, st, P, C, a, (const f16*)y,
-                         scale, shift, relu, coef, (f16*)dy);
-  } else {
-    if (Ci == 32)
-      hipLaunchKernelGGL((bn_bwd_apply_pool_gate_kernel<bf16, 1>), dim3((int)b), dim3(256), 0, st, P, C, a,
-                         (const bf16*)y, scale, shift, relu, coef, (bf16*)dy);
-    else
-      hipLaunchKernelGGL((bn_bwd_apply_pool_gate_kernel<bf16, 2>), dim3((int)b), dim3(256), 0, st, P, C, a,
-                         (const bf16*)y, scale, shift, relu, coef, (bf16*)dy);
-  }
-  return check_launch("bn_bwd_apply_pool_gate");
+  return UNET_DISPATCH_T16(dtype, launch_apply_pool_gate<T>(Ci, (hipStream_t)stream, P, C, a, y, scale, shift, relu, coef,
+                                                            dy));
 }
 
 }  // extern "C"

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 #include "unet_hip.h"
 
 namespace unet {
@@ -113,6 +114,26 @@ int check_launch(const char* what);
 
 inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 
+// channel lanes of a 2-D block (CL channel lanes x 256/CL pixel rows): the power of two >= C, 64 at most
+inline int chan_lanes(int C) {
+  int cl = 1;
+  while (cl < C && cl < 64) cl <<= 1;
+  return cl;
+}
+// 256-thread blocks of a grid-stride launch over `total` items: `cap` at most, 1 at least
+inline int grid_for(long long total, long long cap) {
+  long long b = (total + 255) / 256;
+  if (b > cap) b = cap;
+  if (b < 1) b = 1;
+  return (int)b;
+}
+// block cap of a grid-stride launch (env override: A/B of the per-thread item count)
+inline long long block_cap(const char* env, long long dflt) {
+  const char* e = getenv(env);
+  const long long v = e ? atoll(e) : 0;
+  return v > 0 ? v : dflt;
+}
+
 // 16-byte vector of 8 x 16-bit values <-> 8 floats, for either 16-bit operand type
 template <typename T>
 __device__ __forceinline__ void unpack8_16(const uint4& q, float* v) {
@@ -153,5 +174,10 @@ __device__ __forceinline__ uint4 pack8_16(const float* v) {
   ((code) == UNET_BF16 ? [&]() { using T = bf16; return __VA_ARGS__; }()  \
    : (code) == UNET_F16 ? [&]() { using T = f16; return __VA_ARGS__; }()  \
                         : [&]() { using T = float; return __VA_ARGS__; }())
+// the same for an entry point that serves the two 16-bit types only and has turned UNET_F32 away before it gets
+// here: no float instantiation of `body` exists
+#define UNET_DISPATCH_T16(code, ...)                                \
+  ((code) == UNET_F16 ? [&]() { using T = f16; return __VA_ARGS__; }()    \
+                      : [&]() { using T = bf16; return __VA_ARGS__; }())
 
 }  // namespace unet

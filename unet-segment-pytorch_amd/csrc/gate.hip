@@ -10,13 +10,8 @@
 
 namespace unet {
 
-static inline int chan_lanes_g(int C) {
-  int cl = 1;
-  while (cl < C && cl < 64) cl <<= 1;
-  return cl;
-}
 static inline int rows_for(long long P, int C) {
-  const int cl = chan_lanes_g(C);
+  const int cl = chan_lanes(C);
   const int cblocks = (C + cl - 1) / cl;
   long long r = (2048 + cblocks - 1) / cblocks;
   const long long maxr = (P + 15) / 16;   // >= 16 pixels per block (the 64^2 maps: 1024 blocks, not 256)
@@ -474,6 +469,60 @@ static bool gate_vec_ok(int Ci) {
   return G && G <= 32 && !getenv("UNET_NO_GATE_VEC");
 }
 
+// one launcher per pass, T from the entry point's dtype code (UNET_DISPATCH_T); G != 0: the vectorised kernel
+template <typename T>
+static int launch_psi(int G, hipStream_t st, long long P, int Ci, const void* gw, const void* xw, const float* gab,
+                      const float* xab, const float* wpsi, float* p, float* partial) {
+  const int rows = pix_rows(P);
+  if (G)
+    hipLaunchKernelGGL(psi_vec_kernel<T>, dim3(rows), dim3(256), 0, st, P, Ci, G, (const T*)gw, (const T*)xw, gab, xab,
+                       wpsi, p, partial, rows);
+  else
+    hipLaunchKernelGGL(psi_kernel<T>, dim3(rows), dim3(256), 0, st, P, Ci, (const T*)gw, (const T*)xw, gab, xab, wpsi, p,
+                       partial, rows);
+  return check_launch("gate_psi");
+}
+template <typename T>
+static int launch_gate_bwd1(int G, hipStream_t st, long long P, int Cx, const float* dxs, const void* yx, const float* sx,
+                            const float* bx, int relu, const float* p, const float* psi_ab, const float* psi_mean,
+                            const float* psi_invstd, float* dx, int dx_accum, float* dq, float* partial) {
+  const int rows = pix_rows(P);
+  if (G)
+    hipLaunchKernelGGL(gate_bwd1_vec_kernel<T>, dim3(rows), dim3(256), 0, st, P, Cx, G, dxs, (const T*)yx, sx, bx, relu,
+                       p, psi_ab, psi_mean, psi_invstd, dx, dx_accum, dq, partial, rows);
+  else
+    hipLaunchKernelGGL(gate_bwd1_kernel<T>, dim3(rows), dim3(256), 0, st, P, Cx, dxs, (const T*)yx, sx, bx, relu, p,
+                       psi_ab, psi_mean, psi_invstd, dx, dx_accum, dq, partial, rows);
+  return check_launch("gate_bwd1");
+}
+template <typename T>
+static int launch_gate_bwd2(int G, hipStream_t st, long long P, int Ci, const void* gw, const void* xw, const float* gab,
+                            const float* xab, const float* g_mean, const float* g_invstd, const float* x_mean,
+                            const float* x_invstd, const float* wpsi, const float* dq, const float* p,
+                            const float* psi_coef, float* partial) {
+  const int cl = chan_lanes(Ci), rows = rows_for(P, Ci);
+  if (G)
+    hipLaunchKernelGGL(gate_bwd2_vec_kernel<T>, dim3(rows), dim3(256), 0, st, P, Ci, G, (const T*)gw, (const T*)xw, gab,
+                       xab, g_mean, g_invstd, x_mean, x_invstd, wpsi, dq, p, psi_coef, partial, rows);
+  else
+    hipLaunchKernelGGL(gate_bwd2_kernel<T>, dim3(cdiv(Ci, cl), rows), dim3(256), 0, st, P, Ci, cl, (const T*)gw,
+                       (const T*)xw, gab, xab, g_mean, g_invstd, x_mean, x_invstd, wpsi, dq, p, psi_coef, partial, rows);
+  return check_launch("gate_bwd2");
+}
+template <typename T>
+static int launch_gate_bwd3(int G, hipStream_t st, long long P, int Ci, const void* gw, const void* xw, const float* gab,
+                            const float* xab, const float* wpsi, const float* dq, const float* p, const float* psi_coef,
+                            const float* gcoef, const float* xcoef, void* dgw, void* dxw) {
+  const int cl = chan_lanes(Ci), rows = rows_for(P, Ci);
+  if (G)
+    hipLaunchKernelGGL(gate_bwd3_vec_kernel<T>, dim3(rows), dim3(256), 0, st, P, Ci, G, (const T*)gw, (const T*)xw, gab,
+                       xab, wpsi, dq, p, psi_coef, gcoef, xcoef, (T*)dgw, (T*)dxw, rows);
+  else
+    hipLaunchKernelGGL(gate_bwd3_kernel<T>, dim3(cdiv(Ci, cl), rows), dim3(256), 0, st, P, Ci, cl, (const T*)gw,
+                       (const T*)xw, gab, xab, wpsi, dq, p, psi_coef, gcoef, xcoef, (T*)dgw, (T*)dxw, rows);
+  return check_launch("gate_bwd3");
+}
+
 }  // namespace unet
 
 using namespace unet;
@@ -484,62 +533,14 @@ int unet_gate_psi_rows(long long P) { return pix_rows(P); }
 
 int unet_gate_psi(int dtype, long long P, int Ci, const void* gw, const void* xw, const float* gab, const float* xab,
                   const float* wpsi, float* p, float* partial, void* stream) {
-  const int rows = pix_rows(P);
-  const int G = vec_group(Ci);
-  if (G) {
-    if (dtype == UNET_F16)
-      hipLaunchKernelGGL(psi_vec_kernel<f16>, dim3(rows), dim3(256), 0, (hipStream_t)stream, P, Ci, G,
-                         (const f16*)gw, (const f16*)xw, gab, xab, wpsi, p, partial, rows);
-    else if (dtype == UNET_BF16)
-      hipLaunchKernelGGL(psi_vec_kernel<bf16>, dim3(rows), dim3(256), 0, (hipStream_t)stream, P, Ci, G,
-                         (const bf16*)gw, (const bf16*)xw, gab, xab, wpsi, p, partial, rows);
-    else
-      hipLaunchKernelGGL(psi_vec_kernel<float>, dim3(rows), dim3(256), 0, (hipStream_t)stream, P, Ci, G,
-                         (const float*)gw, (const float*)xw, gab, xab, wpsi, p, partial, rows);
-    return check_launch("gate_psi");
-  }
-  if (dtype == UNET_F16)
-    hipLaunchKernelGGL(psi_kernel<f16>, dim3(rows), dim3(256), 0, (hipStream_t)stream, P, Ci, (const f16*)gw,
-                       (const f16*)xw, gab, xab, wpsi, p, partial, rows);
-  else if (dtype == UNET_BF16)
-    hipLaunchKernelGGL(psi_kernel<bf16>, dim3(rows), dim3(256), 0, (hipStream_t)stream, P, Ci, (const bf16*)gw,
-                       (const bf16*)xw, gab, xab, wpsi, p, partial, rows);
-  else
-    hipLaunchKernelGGL(psi_kernel<float>, dim3(rows), dim3(256), 0, (hipStream_t)stream, P, Ci, (const float*)gw,
-                       (const float*)xw, gab, xab, wpsi, p, partial, rows);
-  return check_launch("gate_psi");
+  return UNET_DISPATCH_T(dtype, launch_psi<T>(vec_group(Ci), (hipStream_t)stream, P, Ci, gw, xw, gab, xab, wpsi, p, partial));
 }
 
 int unet_gate_bwd1(int dtype, long long P, int Cx, const float* dxs, const void* yx, const float* sx, const float* bx,
                    int relu, const float* p, const float* psi_ab, const float* psi_mean, const float* psi_invstd, float* dx,
                    int dx_accum, float* dq, float* partial, void* stream) {
-  const int rows = pix_rows(P);
-  const int G = vec_group(Cx);
-  if (G) {
-    if (dtype == UNET_F16)
-      hipLaunchKernelGGL(gate_bwd1_vec_kernel<f16>, dim3(rows), dim3(256), 0, (hipStream_t)stream, P, Cx, G, dxs,
-                         (const f16*)yx, sx, bx, relu, p, psi_ab, psi_mean, psi_invstd, dx, dx_accum, dq, partial,
-                         rows);
-    else if (dtype == UNET_BF16)
-      hipLaunchKernelGGL(gate_bwd1_vec_kernel<bf16>, dim3(rows), dim3(256), 0, (hipStream_t)stream, P, Cx, G, dxs,
-                         (const bf16*)yx, sx, bx, relu, p, psi_ab, psi_mean, psi_invstd, dx, dx_accum, dq, partial,
-                         rows);
-    else
-      hipLaunchKernelGGL(gate_bwd1_vec_kernel<float>, dim3(rows), dim3(256), 0, (hipStream_t)stream, P, Cx, G, dxs,
-                         (const float*)yx, sx, bx, relu, p, psi_ab, psi_mean, psi_invstd, dx, dx_accum, dq, partial,
-                         rows);
-    return check_launch("gate_bwd1");
-  }
-  if (dtype == UNET_F16)
-    hipLaunchKernelGGL(gate_bwd1_kernel<f16>, dim3(rows), dim3(256), 0, (hipStream_t)stream, P, Cx, dxs,
-                       (const f16*)yx, sx, bx, relu, p, psi_ab, psi_mean, psi_invstd, dx, dx_accum, dq, partial, rows);
-  else if (dtype == UNET_BF16)
-    hipLaunchKernelGGL(gate_bwd1_kernel<bf16>, dim3(rows), dim3(256), 0, (hipStream_t)stream, P, Cx, dxs,
-                       (const bf16*)yx, sx, bx, relu, p, psi_ab, psi_mean, psi_invstd, dx, dx_accum, dq, partial, rows);
-  else
-    hipLaunchKernelGGL(gate_bwd1_kernel<float>, dim3(rows), dim3(256), 0, (hipStream_t)stream, P, Cx, dxs,
-                       (const float*)yx, sx, bx, relu, p, psi_ab, psi_mean, psi_invstd, dx, dx_accum, dq, partial, rows);
-  return check_launch("gate_bwd1");
+  return UNET_DISPATCH_T(dtype, launch_gate_bwd1<T>(vec_group(Cx), (hipStream_t)stream, P, Cx, dxs, yx, sx, bx, relu, p,
+                                                    psi_ab, psi_mean, psi_invstd, dx, dx_accum, dq, partial));
 }
 
 int unet_gate_bwd2_rows(long long P, int Ci) { return rows_for(P, Ci); }
@@ -548,61 +549,17 @@ int unet_gate_bwd2(int dtype, long long P, int Ci, const void* gw, const void* x
                    const float* g_mean, const float* g_invstd, const float* x_mean, const float* x_invstd,
                    const float* wpsi, const float* dq, const float* p, const float* psi_coef, float* partial,
                    void* stream) {
-  const int cl = chan_lanes_g(Ci), rows = rows_for(P, Ci);
-  if (gate_vec_ok(Ci)) {
-    const int G = vec_group(Ci);
-#define UNET_G2V(TT)                                                                                                \
-  hipLaunchKernelGGL(gate_bwd2_vec_kernel<TT>, dim3(rows), dim3(256), 0, (hipStream_t)stream, P, Ci, G, (const TT*)gw, \
-                     (const TT*)xw, gab, xab, g_mean, g_invstd, x_mean, x_invstd, wpsi, dq, p, psi_coef, partial, rows)
-    if (dtype == UNET_F16) UNET_G2V(f16);
-    else if (dtype == UNET_BF16) UNET_G2V(bf16);
-    else UNET_G2V(float);
-#undef UNET_G2V
-    return check_launch("gate_bwd2");
-  }
-  dim3 grid(cdiv(Ci, cl), rows);
-  if (dtype == UNET_F16)
-    hipLaunchKernelGGL(gate_bwd2_kernel<f16>, grid, dim3(256), 0, (hipStream_t)stream, P, Ci, cl, (const f16*)gw,
-                       (const f16*)xw, gab, xab, g_mean, g_invstd, x_mean, x_invstd, wpsi, dq, p, psi_coef, partial,
-                       rows);
-  else if (dtype == UNET_BF16)
-    hipLaunchKernelGGL(gate_bwd2_kernel<bf16>, grid, dim3(256), 0, (hipStream_t)stream, P, Ci, cl, (const bf16*)gw,
-                       (const bf16*)xw, gab, xab, g_mean, g_invstd, x_mean, x_invstd, wpsi, dq, p, psi_coef, partial,
-                       rows);
-  else
-    hipLaunchKernelGGL(gate_bwd2_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, P, Ci, cl, (const float*)gw,
-                       (const float*)xw, gab, xab, g_mean, g_invstd, x_mean, x_invstd, wpsi, dq, p, psi_coef, partial,
-                       rows);
-  return check_launch("gate_bwd2");
+  const int G = gate_vec_ok(Ci) ? vec_group(Ci) : 0;
+  return UNET_DISPATCH_T(dtype, launch_gate_bwd2<T>(G, (hipStream_t)stream, P, Ci, gw, xw, gab, xab, g_mean, g_invstd, x_mean,
+                                                    x_invstd, wpsi, dq, p, psi_coef, partial));
 }
 
 int unet_gate_bwd3(int dtype, long long P, int Ci, const void* gw, const void* xw, const float* gab, const float* xab,
                    const float* wpsi, const float* dq, const float* p, const float* psi_coef, const float* gcoef,
                    const float* xcoef, void* dgw, void* dxw, void* stream) {
-  const int cl = chan_lanes_g(Ci), rows = rows_for(P, Ci);
-  if (gate_vec_ok(Ci)) {
-    const int G = vec_group(Ci);
-#define UNET_G3V(TT)                                                                                                \
-  hipLaunchKernelGGL(gate_bwd3_vec_kernel<TT>, dim3(rows), dim3(256), 0, (hipStream_t)stream, P, Ci, G, (const TT*)gw, \
-                     (const TT*)xw, gab, xab, wpsi, dq, p, psi_coef, gcoef, xcoef, (TT*)dgw, (TT*)dxw, rows)
-    if (dtype == UNET_F16) UNET_G3V(f16);
-    else if (dtype == UNET_BF16) UNET_G3V(bf16);
-    else UNET_G3V(float);
-#undef UNET_G3V
-    return check_launch("gate_bwd3");
-  }
-  dim3 grid(cdiv(Ci, cl), rows);
-  if (dtype == UNET_F16)
-    hipLaunchKernelGGL(gate_bwd3_kernel<f16>, grid, dim3(256), 0, (hipStream_t)stream, P, Ci, cl, (const f16*)gw,
-                       (const f16*)xw, gab, xab, wpsi, dq, p, psi_coef, gcoef, xcoef, (f16*)dgw, (f16*)dxw, rows);
-  else if (dtype == UNET_BF16)
-    hipLaunchKernelGGL(gate_bwd3_kernel<bf16>, grid, dim3(256), 0, (hipStream_t)stream, P, Ci, cl, (const bf16*)gw,
-                       (const bf16*)xw, gab, xab, wpsi, dq, p, psi_coef, gcoef, xcoef, (bf16*)dgw, (bf16*)dxw, rows);
-  else
-    hipLaunchKernelGGL(gate_bwd3_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, P, Ci, cl, (const float*)gw,
-                       (const float*)xw, gab, xab, wpsi, dq, p, psi_coef, gcoef, xcoef, (float*)dgw, (float*)dxw,
-                       rows);
-  return check_launch("gate_bwd3");
+  const int G = gate_vec_ok(Ci) ? vec_group(Ci) : 0;
+  return UNET_DISPATCH_T(dtype, launch_gate_bwd3<T>(G, (hipStream_t)stream, P, Ci, gw, xw, gab, xab, wpsi, dq, p, psi_coef,
+                                                    gcoef, xcoef, dgw, dxw));
 }
 
 }  // extern "C"

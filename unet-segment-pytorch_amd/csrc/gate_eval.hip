@@ -167,7 +167,7 @@ int unet_gate_psi_eval(int dtype, long long P, int Cg, int Cx, int Ci, const voi
   }
   GateEvalArgs a{P, Cg, Cx, Ci, g, x, xs, xb, xrelu, wg_packed, wx_packed, gab, xab, wpsi, p};
   hipStream_t st = (hipStream_t)stream;
-  return dtype == UNET_BF16 ? launch_gate_eval<bf16>(a, st) : launch_gate_eval<f16>(a, st);
+  return UNET_DISPATCH_T16(dtype, launch_gate_eval<T>(a, st));
 }
 
 }  // extern "C"

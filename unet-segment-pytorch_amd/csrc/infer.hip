@@ -122,12 +122,6 @@ __global__ void postprocess_mask_kernel(long long N, int K, int H, int W, const 
   }
 }
 
-static int grid_for(long long total) {
-  long long b = (total + 255) / 256;
-  if (b > 16384) b = 16384;
-  return (int)(b < 1 ? 1 : b);
-}
-
 }  // namespace unet
 
 using namespace unet;
@@ -143,11 +137,11 @@ int unet_resample_u8(int axis, long long N, int inH, int inW, int out_len, const
   hipStream_t st = (hipStream_t)stream;
   if (axis == 1) {
     const long long total = N * inH * (long long)out_len;
-    hipLaunchKernelGGL(resample_h_kernel, dim3(grid_for(total)), dim3(256), 0, st, N, inH, inW, out_len, in, roundtrip,
+    hipLaunchKernelGGL(resample_h_kernel, dim3(grid_for(total, 16384)), dim3(256), 0, st, N, inH, inW, out_len, in, roundtrip,
                        bounds, coeffs, ksize, out);
   } else {
     const long long total = N * (long long)out_len * inW;
-    hipLaunchKernelGGL(resample_v_kernel, dim3(grid_for(total)), dim3(256), 0, st, N, inH, inW, out_len, in, roundtrip,
+    hipLaunchKernelGGL(resample_v_kernel, dim3(grid_for(total, 16384)), dim3(256), 0, st, N, inH, inW, out_len, in, roundtrip,
                        bounds, coeffs, ksize, out);
   }
   return check_launch("resample_u8");
@@ -163,11 +157,11 @@ int unet_slice_finish(long long N, int H, int W, const uint8_t* img, int roundtr
   }
   hipStream_t st = (hipStream_t)stream;
   const long long total = N * (long long)H * W;
-  hipLaunchKernelGGL(image_finish_kernel, dim3(grid_for(total)), dim3(256), 0, st, N, H, W, img, roundtrip, flip, mean,
+  hipLaunchKernelGGL(image_finish_kernel, dim3(grid_for(total, 16384)), dim3(256), 0, st, N, H, W, img, roundtrip, flip, mean,
                      stdv, out_img);
   if (int rc = check_launch("image_finish")) return rc;
   if (mask)
-    hipLaunchKernelGGL(mask_finish_kernel, dim3(grid_for(total)), dim3(256), 0, st, N, mask_h, mask_w, mask, H, W, ytab,
+    hipLaunchKernelGGL(mask_finish_kernel, dim3(grid_for(total, 16384)), dim3(256), 0, st, N, mask_h, mask_w, mask, H, W, ytab,
                        xtab, flip, out_mask);
   return check_launch("mask_finish");
 }
@@ -180,7 +174,7 @@ int unet_postprocess_mask(long long N, int K, int H, int W, const float* logits,
     return UNET_ERR_ARG;
   }
   const long long total = N * (long long)outH * outW;
-  hipLaunchKernelGGL(postprocess_mask_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, N, K, H, W,
+  hipLaunchKernelGGL(postprocess_mask_kernel, dim3(grid_for(total, 16384)), dim3(256), 0, (hipStream_t)stream, N, K, H, W,
                      logits, cls, threshold, outH, outW, ytab, xtab, out);
   return check_launch("postprocess_mask");
 }

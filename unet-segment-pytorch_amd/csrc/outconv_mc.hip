@@ -1,12 +1,12 @@
 // outconv_mc.hip — OutConv for 9..16 classes on MFMA ("mc": multi-class): forward and backward.
 //
 // Reference: OutConv = nn.Conv2d(C, n_classes, kernel_size=1) with bias (unet/models/layers.py:109-123) and its
-// convolution_backward.  misc.hip serves n_classes <= 8 with per-class scalar / shuffle kernels whose register and
+// convolution_backward.  outconv.hip serves n_classes <= 8 with per-class scalar / shuffle kernels whose register and
 // shuffle cost grows with the class count; sixteen classes are exactly one MFMA row tile, so here the class axis
 // sits on an MFMA dimension and the channel (forward) or pixel (weight gradient) reduction happens inside the
 // matrix instruction.  One kernel serves every K in [9, 16]: class rows K..15 are zero weights and are never stored.
 //
-// Operand convention (the conv kernels', not misc.hip's fp32 math): the activation is one fmaf(y, scale, shift) in
+// Operand convention (the conv kernels', not outconv.hip's fp32 math): the activation is one fmaf(y, scale, shift) in
 // fp32 (exact ReLU mask), clamped, then rounded to the operand type T; w and dl are rounded to T where they enter an
 // MFMA; accumulation is fp32; db = Σ dl is summed from the unrounded fp32 dl.  In fp32 mode nothing is rounded
 // (16x16x4 f32).

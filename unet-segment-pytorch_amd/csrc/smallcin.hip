@@ -448,25 +448,23 @@ int smallcin_stats_rows(const unet_conv_desc* d) {
 
 bool smallcin_is_mfma(const unet_conv_desc* d) { return smallcin_mfma_ok(d); }
 
-int smallcin_conv(const unet_conv_desc* d, hipStream_t st) {
-  if (smallcin_mfma_ok(d)) {
-    const int t = smallcin_mfma_tiles(d);
-    const int grid = t < SCM_GRID ? t : SCM_GRID;
-    if (d->dtype == UNET_BF16)
-      hipLaunchKernelGGL(smallcin_fwd_mfma_kernel<bf16>, dim3(grid), dim3(256), 0, st, *d, t);
-    else
-      hipLaunchKernelGGL(smallcin_fwd_mfma_kernel<f16>, dim3(grid), dim3(256), 0, st, *d, t);
-    return check_launch("smallcin_fwd_mfma");
-  }
-  if (d->Cout > 64) { set_error("smallcin: Cout > 64"); return UNET_ERR_UNSUPPORTED; }
+template <typename T>
+static int launch_smallcin_fwd_mfma(const unet_conv_desc* d, hipStream_t st) {
+  const int t = smallcin_mfma_tiles(d);
+  hipLaunchKernelGGL(smallcin_fwd_mfma_kernel<T>, dim3(t < SCM_GRID ? t : SCM_GRID), dim3(256), 0, st, *d, t);
+  return check_launch("smallcin_fwd_mfma");
+}
+template <typename T>
+static int launch_smallcin_fwd(const unet_conv_desc* d, hipStream_t st) {
   const int rows = smallcin_rows((long long)d->N * d->H * d->W);
-  if (d->dtype == UNET_BF16)
-    hipLaunchKernelGGL(smallcin_fwd_kernel<bf16>, dim3(rows), dim3(256), 0, st, *d, rows);
-  else if (d->dtype == UNET_F16)
-    hipLaunchKernelGGL(smallcin_fwd_kernel<f16>, dim3(rows), dim3(256), 0, st, *d, rows);
-  else
-    hipLaunchKernelGGL(smallcin_fwd_kernel<float>, dim3(rows), dim3(256), 0, st, *d, rows);
+  hipLaunchKernelGGL(smallcin_fwd_kernel<T>, dim3(rows), dim3(256), 0, st, *d, rows);
   return check_launch("smallcin_fwd");
+}
+
+int smallcin_conv(const unet_conv_desc* d, hipStream_t st) {
+  if (smallcin_mfma_ok(d)) return UNET_DISPATCH_T16(d->dtype, launch_smallcin_fwd_mfma<T>(d, st));
+  if (d->Cout > 64) { set_error("smallcin: Cout > 64"); return UNET_ERR_UNSUPPORTED; }
+  return UNET_DISPATCH_T(d->dtype, launch_smallcin_fwd<T>(d, st));
 }
 
 // weight gradient on MFMA (16-bit dy, Cout = 64, Cin <= 3): D[co][k] = Σ_px dy[px][co] X[px][k], K = the
@@ -678,16 +676,23 @@ size_t smallcin_wgrad_ws(const unet_wgrad_desc* d) {
   return (size_t)smallcin_rows((long long)d->N * d->H * d->W) * d->Cout * d->Cin * 9 * sizeof(float);
 }
 
+template <typename T>
+static int launch_smallcin_wgrad_mfma(const unet_wgrad_desc* d, int grid, int tiles, float* part, hipStream_t st) {
+  hipLaunchKernelGGL(smallcin_wgrad_mfma_kernel<T>, dim3(grid), dim3(256), 0, st, *d, tiles, part);
+  return check_launch("smallcin_wgrad_mfma");
+}
+template <typename T>
+static int launch_smallcin_wgrad(const unet_wgrad_desc* d, int rows, float* part, hipStream_t st) {
+  hipLaunchKernelGGL(smallcin_wgrad_kernel<T>, dim3(rows), dim3(256), 0, st, *d, rows, part);
+  return check_launch("smallcin_wgrad");
+}
+
 int smallcin_wgrad(const unet_wgrad_desc* d, hipStream_t st) {
   if (smallcin_wgrad_mfma_ok(d)) {
     int t;
     const int grid = smallcin_wgrad_grid(d, &t);
     float* part = (float*)d->workspace;
-    if (d->dtype == UNET_BF16)
-      hipLaunchKernelGGL(smallcin_wgrad_mfma_kernel<bf16>, dim3(grid), dim3(256), 0, st, *d, t, part);
-    else
-      hipLaunchKernelGGL(smallcin_wgrad_mfma_kernel<f16>, dim3(grid), dim3(256), 0, st, *d, t, part);
-    int e = check_launch("smallcin_wgrad_mfma");
+    int e = UNET_DISPATCH_T16(d->dtype, launch_smallcin_wgrad_mfma<T>(d, grid, t, part, st));
     if (e) return e;
     const int rows = 4 * grid, W = 64 * 2 * 9 * d->Cin, nb = cdiv(rows, SCF_R);
     float* sums = part + (size_t)rows * W;   // after the partial table (smallcin_wgrad_ws)
@@ -705,13 +710,7 @@ int smallcin_wgrad(const unet_wgrad_desc* d, hipStream_t st) {
   }
   const int rows = smallcin_rows((long long)d->N * d->H * d->W);
   float* part = (float*)d->workspace;
-  if (d->dtype == UNET_BF16)
-    hipLaunchKernelGGL(smallcin_wgrad_kernel<bf16>, dim3(rows), dim3(256), 0, st, *d, rows, part);
-  else if (d->dtype == UNET_F16)
-    hipLaunchKernelGGL(smallcin_wgrad_kernel<f16>, dim3(rows), dim3(256), 0, st, *d, rows, part);
-  else
-    hipLaunchKernelGGL(smallcin_wgrad_kernel<float>, dim3(rows), dim3(256), 0, st, *d, rows, part);
-  int e = check_launch("smallcin_wgrad");
+  int e = UNET_DISPATCH_T(d->dtype, launch_smallcin_wgrad<T>(d, rows, part, st));
   if (e) return e;
   return unet_colsum(part, rows, d->Cout * d->Cin * 9, d->dw, d->accum, (void*)st);
 }

@@ -803,7 +803,7 @@ class OutConvStage:
         self.sole_consumer = sole_consumer
 
     def _entry(self, prec, a: Act, which: str) -> str:
-        """n_classes <= 8: the misc.hip kernels; 9..16: the MFMA kernels of outconv_mc.hip (entry points of their
+        """n_classes <= 8: the outconv.hip kernels; 9..16: the MFMA kernels of outconv_mc.hip (entry points of their
         own; nothing falls back from one to the other)."""
         if self.k <= 8:
             return f"unet_outconv_{which}"
