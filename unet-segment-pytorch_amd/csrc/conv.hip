@@ -511,7 +511,7 @@ static bool fast_eligible(const unet_conv_desc* d) {
   return true;
 }
 
-// the one place that chooses d's kernel family, in priority order: smallcin, pw, generic (sources the pipelined
+// the one place that chooses d's kernel family, in priority order: smallcin, stem, pw, generic (sources the pipelined
 // kernels cannot load), the conv5 forms (16-bit), conv3, conv2.  The split-K form is chosen only with a
 // non-null d->workspace; r.c5.workspace sizes it from the shape either way.
 ConvRoute conv_route(const unet_conv_desc* d) {
@@ -519,6 +519,9 @@ ConvRoute conv_route(const unet_conv_desc* d) {
   if (smallcin_conv_ok(d)) {
     r.path = CONV_SMALLCIN;
     r.stats_rows = smallcin_stats_rows(d);
+  } else if (stem_conv_ok(d)) {
+    r.path = CONV_STEM;
+    r.stats_rows = stem_stats_rows(d);
   } else if (pw_conv_ok(d)) {
     r.path = CONV_PW;
     r.stats_rows = pw_conv_rows(d);
@@ -631,6 +634,7 @@ int unet_conv_variant(const unet_conv_desc* d, char* buf, int len) {
     case CONV_SMALLCIN:
       snprintf(buf, len, smallcin_is_mfma(d) ? "smallcin_fwd_mfma_kernel<%s>" : "smallcin_fwd_kernel<%s>", tn);
       break;
+    case CONV_STEM: snprintf(buf, len, "stem_fwd_mfma_kernel<%s,%d>", tn, d->Cout); break;
     case CONV_PW: return pw_conv_variant(d, buf, len);
     case CONV_GENERIC: snprintf(buf, len, "conv_generic_kernel<%s,%d,%d>", tn, d->ksize, d->Cout <= 32 ? 32 : 64); break;
     case CONV_CONV5W: snprintf(buf, len, r.c5.mi == 4 ? "conv5w_kernel<%s,4>" : "conv5w_kernel<%s>", tn); break;
@@ -755,6 +759,7 @@ int unet_conv(const unet_conv_desc* d, void* stream) {
   int rc = UNET_ERR_ARG;
   switch (r.path) {
     case CONV_SMALLCIN: rc = smallcin_conv(d, st); break;
+    case CONV_STEM: rc = stem_conv(d, st); break;
     case CONV_PW: rc = pw_conv(d, st); break;
     case CONV_GENERIC: rc = conv_generic(d, st); break;
     case CONV_CONV5W:

@@ -43,6 +43,9 @@ bool smallcin_conv_ok(const unet_conv_desc* d);     // smallcin.hip
 int smallcin_stats_rows(const unet_conv_desc* d);
 bool smallcin_is_mfma(const unet_conv_desc* d);
 int smallcin_conv(const unet_conv_desc* d, hipStream_t st);
+bool stem_conv_ok(const unet_conv_desc* d);         // stem.hip: fp32 NCHW input, 5 <= Cin <= 16, on MFMA
+int stem_stats_rows(const unet_conv_desc* d);
+int stem_conv(const unet_conv_desc* d, hipStream_t st);
 bool pw_conv_ok(const unet_conv_desc* d);           // pw.hip
 int pw_conv_rows(const unet_conv_desc* d);
 int pw_conv(const unet_conv_desc* d, hipStream_t st);
@@ -57,7 +60,7 @@ struct ConvTile {
   int wm, wn, ntn, mi, raw;
 };
 
-enum ConvPath { CONV_SMALLCIN, CONV_PW, CONV_GENERIC, CONV_CONV5W, CONV_CONV5, CONV_CONV5_SPLITK, CONV_CONV3, CONV_CONV2 };
+enum ConvPath { CONV_SMALLCIN, CONV_STEM, CONV_PW, CONV_GENERIC, CONV_CONV5W, CONV_CONV5, CONV_CONV5_SPLITK, CONV_CONV3, CONV_CONV2 };
 struct ConvRoute {
   ConvPath path;
   ConvTile tile;          // CONV_CONV3 / CONV_CONV2
@@ -68,7 +71,7 @@ struct ConvRoute {
 ConvRoute conv_route(const unet_conv_desc* d);   // conv.hip
 
 // ---- weight gradients ----------------------------------------------------------------------------
-enum WgradPath { WGRAD_SMALLCIN, WGRAD_PW, WGRAD_WGRAD5, WGRAD_WGRAD2, WGRAD_WGRAD };
+enum WgradPath { WGRAD_SMALLCIN, WGRAD_STEM, WGRAD_PW, WGRAD_WGRAD5, WGRAD_WGRAD2, WGRAD_WGRAD };
 struct WgradRoute {
   WgradPath path;
   size_t workspace;   // bytes unet_conv_wgrad needs in d->workspace
@@ -80,6 +83,9 @@ bool smallcin_wgrad_ok(const unet_wgrad_desc* d);   // smallcin.hip
 size_t smallcin_wgrad_ws(const unet_wgrad_desc* d);
 bool smallcin_wgrad_is_mfma(const unet_wgrad_desc* d);
 int smallcin_wgrad(const unet_wgrad_desc* d, hipStream_t st);
+bool stem_wgrad_ok(const unet_wgrad_desc* d);       // stem.hip
+size_t stem_wgrad_ws(const unet_wgrad_desc* d);
+int stem_wgrad(const unet_wgrad_desc* d, hipStream_t st);
 bool pw_wgrad_ok(const unet_wgrad_desc* d);         // pw.hip
 size_t pw_wgrad_ws(const unet_wgrad_desc* d);
 int pw_wgrad(const unet_wgrad_desc* d, hipStream_t st);

@@ -231,6 +231,10 @@ WgradRoute wgrad_route(const unet_wgrad_desc* d) {
     r.path = WGRAD_SMALLCIN;
     r.workspace = smallcin_wgrad_ws(d);
     snprintf(r.variant, sizeof(r.variant), smallcin_wgrad_is_mfma(d) ? "smallcin_wgrad_mfma_kernel<%s>" : "smallcin_wgrad_kernel<%s>", tn);
+  } else if (stem_wgrad_ok(d)) {
+    r.path = WGRAD_STEM;
+    r.workspace = stem_wgrad_ws(d);
+    snprintf(r.variant, sizeof(r.variant), "stem_wgrad_mfma_kernel<%s,%d>", tn, d->Cout);
   } else if (pw_wgrad_ok(d)) {
     r.path = WGRAD_PW;
     r.workspace = pw_wgrad_ws(d);
@@ -278,6 +282,7 @@ int unet_conv_wgrad(const unet_wgrad_desc* d, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   switch (wgrad_route(d).path) {
     case WGRAD_SMALLCIN: return smallcin_wgrad(d, st);
+    case WGRAD_STEM: return stem_wgrad(d, st);
     case WGRAD_PW: return pw_wgrad(d, st);
     case WGRAD_WGRAD5: return wgrad5_run(d, st);
     case WGRAD_WGRAD2: return wgrad2_run(d, st);
