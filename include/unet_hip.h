@@ -30,8 +30,9 @@ extern "C" {
  * a caller built against an older header must not pass its (shorter) descriptors to this library.
  * 111: unet_aug_params, unet_aug_elastic_field and unet_aug_apply added (no existing layout changed)
  * 114: the optimizer tail (unet_optim_*, unet_ema_update) added (no existing layout changed)
- * 115: the multi-class cross-entropy / Dice + CE loss (unet_ce_*) added (no existing layout changed) */
-#define UNET_ABI_VERSION 115
+ * 115: the multi-class cross-entropy / Dice + CE loss (unet_ce_*) added (no existing layout changed)
+ * 116: the surface-distance metrics (unet_surface_*) added (no existing layout changed) */
+#define UNET_ABI_VERSION 116
 
 enum { UNET_F32 = 0, UNET_BF16 = 1, UNET_F16 = 2 };  /* operand (activation / weight) type */
 enum { UNET_ERR_ARG = 1001, UNET_ERR_UNSUPPORTED = 1002 };
@@ -383,6 +384,23 @@ int unet_confusion_matrix(long long N, int C, int K, long long HW, const float* 
  * |pred == c| / |target == c| are the column / row sums; logits have C channels (C may differ from K). */
 int unet_confusion_matrix_ext(long long N, int C, int K, long long HW, const float* logits, const int64_t* labels,
                               const int64_t* targets, int64_t* confusion, void* stream);
+
+/* ---- surface-distance metrics: Hausdorff, its percentile (HD95) and ASSD (csrc/surface.hip) --
+ * Label maps P (argmax over the C fp32 NCHW logit channels by unet_confusion_matrix's rule, or the int64 labels
+ * when logits == NULL) and T = targets, both (N, H, W); a label outside [0, K) belongs to no class.  For class c
+ * of image n, A = (P == c), B = (T == c); the surface S(A) is every pixel of A with a 4-neighbour outside A
+ * (outside the frame is outside A).  d(a, S(B)) = min_b sqrt(sy^2 (ya-yb)^2 + sx^2 (xa-xb)^2).  Outputs, device
+ * [N][K]: hd = the larger directed maximum; hd_percentile = the larger directed quantile (numpy.percentile's
+ * linear interpolation at rank quantile * (m - 1), quantile = q / 100 in [0, 1]); assd = (sum_a d(a, S(B)) +
+ * sum_b d(b, S(A))) / (|S(A)| + |S(B)|); n_pred = |S(A)|, n_true = |S(B)|.  The three distances are NaN where
+ * either surface is empty.  1 <= K <= 16, 1 <= H, W <= 2048, N * K <= 65535, sy, sx > 0 (else UNET_ERR_ARG).
+ * No floating-point atomics: bit-identical from run to run.  workspace: unet_surface_workspace bytes
+ * (0 for an unsupported shape), 16-byte aligned, contents undefined on entry and on return.                  */
+size_t unet_surface_workspace(long long N, int K, int H, int W);
+int unet_surface_distances(long long N, int C, int K, int H, int W, const float* logits, const int64_t* labels,
+                           const int64_t* targets, double sy, double sx, double quantile, void* workspace,
+                           double* hd, double* hd_percentile, double* assd, int64_t* n_pred, int64_t* n_true,
+                           void* stream);
 
 /* ---- DiceBCE / Dice / BalancedCE loss + grad — loss.py:18-191 ------------------------------- */
 int unet_loss_rows(long long HW);

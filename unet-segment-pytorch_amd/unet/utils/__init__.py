@@ -4,11 +4,12 @@ training step).  The reference's host-side callbacks/plots/dataset are out of sc
 
 from .loss import (DiceLoss, BalancedCELoss, DiceBCELoss, CrossEntropyLoss, DiceCELoss, DeepSupervisionLoss,
                    create_loss_function)
-from .metrics import SegmentationMetrics, compute_dice, compute_iou
+from .metrics import (SegmentationMetrics, compute_dice, compute_iou, surface_distances,
+                      SurfaceDistanceMetrics)
 from .config import load_config, create_model, create_criterion, build_from_config, create_train_transform
 from .optim import FusedClipAdamW
 from .general import ModelEMA
 
 __all__ = ["FusedClipAdamW", "ModelEMA","DiceLoss", "BalancedCELoss", "DiceBCELoss", "CrossEntropyLoss", "DiceCELoss", "DeepSupervisionLoss", "create_loss_function",
-           "SegmentationMetrics", "compute_iou", "compute_dice", "load_config", "create_model", "create_criterion",
+           "SegmentationMetrics", "compute_iou", "compute_dice", "surface_distances", "SurfaceDistanceMetrics", "load_config", "create_model", "create_criterion",
            "build_from_config", "create_train_transform"]
