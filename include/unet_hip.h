@@ -31,8 +31,9 @@ extern "C" {
  * 111: unet_aug_params, unet_aug_elastic_field and unet_aug_apply added (no existing layout changed)
  * 114: the optimizer tail (unet_optim_*, unet_ema_update) added (no existing layout changed)
  * 115: the multi-class cross-entropy / Dice + CE loss (unet_ce_*) added (no existing layout changed)
- * 116: the surface-distance metrics (unet_surface_*) added (no existing layout changed) */
-#define UNET_ABI_VERSION 116
+ * 116: the surface-distance metrics (unet_surface_*) added (no existing layout changed)
+ * 117: connected-component labelling and filtering (unet_cc_*) added, no existing layout changed */
+#define UNET_ABI_VERSION 117
 
 enum { UNET_F32 = 0, UNET_BF16 = 1, UNET_F16 = 2 };  /* operand (activation / weight) type */
 enum { UNET_ERR_ARG = 1001, UNET_ERR_UNSUPPORTED = 1002 };
@@ -401,6 +402,31 @@ int unet_surface_distances(long long N, int C, int K, int H, int W, const float*
                            const int64_t* targets, double sy, double sx, double quantile, void* workspace,
                            double* hd, double* hd_percentile, double* assd, int64_t* n_pred, int64_t* n_true,
                            void* stream);
+
+/* ---- connected components of a label map: labelling and size filtering (csrc/cc.hip) ----------
+ * The label map P (N, H, W) is the argmax over the C fp32 NCHW logit channels (unet_confusion_matrix's rule), the
+ * int64 labels, or a uint8 mask (byte > 127: class 1, else class 0; K must be 2): exactly one of the three is
+ * non-NULL.  A label outside [0, K) belongs to no class; pixels of class `background` (-1: none) are not labelled.
+ * A component is a maximal set of pixels of one class connected through 4- or 8-neighbourhoods (`connectivity`);
+ * its id is the smallest linear index y * W + x of its pixels within the image.  Outputs, device:
+ *   comp  int32 [N][H][W]  the component id, -1 for background and no-class pixels
+ *   area  int32 [N][H][W]  the component's pixel count at its id pixel, 0 elsewhere
+ *   cls   uint8 [N][H][W]  the class, 255 for no class
+ *   count int64 [N][K]     components per image and class (overwritten)
+ * unet_cc_filter keeps a component iff area >= min_size and, with keep_largest != 0, it is the largest of its
+ * (image, class), the smaller id on a tie.  Exactly one output is non-NULL.  out_labels int64: the class of kept
+ * components, `background` on background pixels, `fill` elsewhere; out_mask uint8: 255 on kept components of
+ * class 1, else 0.  1 <= K <= 16, -1 <= background < K, connectivity 4 or 8 (else UNET_ERR_ARG); 1 <= H, W <= 4096
+ * and N * H * W < 2^31 (else UNET_ERR_UNSUPPORTED, and the workspace query returns 0).  Integer atomics only:
+ * bit-identical from run to run.  workspace: unet_cc_workspace bytes for both calls, 16-byte aligned, contents
+ * undefined on entry and on return.                                                                            */
+size_t unet_cc_workspace(long long N, int H, int W);
+int unet_cc_label(long long N, int C, int K, int H, int W, const float* logits, const int64_t* labels,
+                  const uint8_t* mask, int connectivity, int background, void* workspace, int32_t* comp,
+                  int32_t* area, uint8_t* cls, int64_t* count, void* stream);
+int unet_cc_filter(long long N, int K, int H, int W, const int32_t* comp, const int32_t* area, const uint8_t* cls,
+                   long long min_size, int keep_largest, int background, long long fill, void* workspace,
+                   int64_t* out_labels, uint8_t* out_mask, void* stream);
 
 /* ---- DiceBCE / Dice / BalancedCE loss + grad — loss.py:18-191 ------------------------------- */
 int unet_loss_rows(long long HW);

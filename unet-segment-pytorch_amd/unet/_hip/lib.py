@@ -174,6 +174,11 @@ _SIGS = {
     "unet_surface_workspace": (c_size, [c_ll, c_int, c_int, c_int]),
     "unet_surface_distances": (c_int, [c_ll, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, ctypes.c_double,
                                        ctypes.c_double, ctypes.c_double, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "unet_cc_workspace": (c_size, [c_ll, c_int, c_int]),
+    "unet_cc_label": (c_int, [c_ll, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_vp,
+                              c_vp, c_vp, c_vp]),
+    "unet_cc_filter": (c_int, [c_ll, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_ll, c_int, c_int, c_ll, c_vp, c_vp,
+                               c_vp, c_vp]),
     "unet_loss_rows": (c_int, [c_ll]),
     "unet_loss_reduce": (c_int, [c_ll, c_int, c_ll, c_vp, c_vp, c_vp, c_vp]),
     "unet_loss_finalize": (c_int, [c_vp, c_int, c_ll, c_int, c_float, c_float, c_float, c_float, c_float, c_int, c_int,
@@ -211,7 +216,7 @@ _SIGS = {
 }
 
 _lib = None
-ABI_VERSION = 116 # include/unet_hip.h UNET_ABI_VERSION
+ABI_VERSION = 117 # include/unet_hip.h UNET_ABI_VERSION
 
 # UNET_GUARD=1: bounds-checking debug mode (csrc/guard_alloc.cpp).  Every device allocation of the process
 # gets guard bands and every library call is bracketed by a device sync + a check of all bands, so an
@@ -224,7 +229,7 @@ _NO_LAUNCH = {"unet_last_error", "unet_version", "unet_conv_mtiles", "unet_conv_
               "unet_wgrad_variant", "unet_conv_act_out_ok", "unet_conv_workspace", "unet_packed_weight_elems", "unet_wgrad_workspace",
               "unet_bn_bwd_reduce_rows", "unet_gate_psi_rows", "unet_gate_bwd2_rows", "unet_convt_bwd_rows",
               "unet_outconv_rows", "unet_outconv_mc_ok", "unet_loss_rows", "unet_upsample_bwd_pw_ok", "unet_bn_bwd_pool_gate_ok",
-              "unet_optim_chunks", "unet_surface_workspace"}
+              "unet_optim_chunks", "unet_surface_workspace", "unet_cc_workspace"}
 
 
 class HipLibraryError(RuntimeError):

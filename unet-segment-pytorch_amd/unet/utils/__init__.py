@@ -9,7 +9,8 @@ from .metrics import (SegmentationMetrics, compute_dice, compute_iou, surface_di
 from .config import load_config, create_model, create_criterion, build_from_config, create_train_transform
 from .optim import FusedClipAdamW
 from .general import ModelEMA
+from .inference import connected_components, filter_components
 
 __all__ = ["FusedClipAdamW", "ModelEMA","DiceLoss", "BalancedCELoss", "DiceBCELoss", "CrossEntropyLoss", "DiceCELoss", "DeepSupervisionLoss", "create_loss_function",
            "SegmentationMetrics", "compute_iou", "compute_dice", "surface_distances", "SurfaceDistanceMetrics", "load_config", "create_model", "create_criterion",
-           "build_from_config", "create_train_transform"]
+           "build_from_config", "create_train_transform", "connected_components", "filter_components"]
